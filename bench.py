@@ -11,7 +11,10 @@ Adam/Noam, on a synthetic batch already resident in HBM.  Workload = BASELINE.js
 T_text=160, T_mel=800, 80 mels, 12 flow blocks, n_split=4, fp32, ModelConfig defaults (dropout 0.1 / 0.05 active),
 random-init weights, data-dependent ActNorm init done before timing.  Weak scaling: every rank gets its own B=32.
 
-Rank 0 prints ONE JSON line.  Besides the driver's contract it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the --steps steps, writes the last step's outputs when
+--dump-outputs DIR is given and prints the line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` and the
+run's configuration.  With --full, legs run after the timed steps add
+  "native_fp32"  : the same step with the WN convolutions in the other arithmetic (`split_math` when fp32 is the default);
   "roofline"     : the dominant hand-written HIP launch of the step, chosen MECHANICALLY: arg-max of launches per step x mean
                    duration over the table of launches the step makes (`as_launched_top5`).  Mean durations come from an
                    instrumented pass after the timed region (HIP events on the launch stream around every launch); the two
@@ -89,7 +92,20 @@ def parse():
     ap.add_argument("--graph", action="store_true",
                     help="replay the step from a captured hipGraph (GraphedTrainStep); default is eager launches — the step is "
                          "GPU-bound, so replay buys <1 %% at this shape")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the diagnostic legs: the other conv arithmetic, the roofline pass, "
+                         "BASELINE configs[2] / configs[4] and the CPU baseline (each can still be dropped by its --no-* "
+                         "option); without it a run times the step and nothing else")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy: the loss (float64) and a "
+                         "fixed, seeded sample of the updated parameters and of their gradients (float32); that step starts "
+                         "from the state after set-up, so its inputs are the same in every run")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        args.no_split_math = args.no_roofline = args.no_other_configs = args.no_cpu_baseline = True
+    return args
 
 
 def algorithmic_bytes(B, C, H, Ts, T_text, n_params_padded):
@@ -568,6 +584,26 @@ def build_workload(args, dev, rank):
     return model, opt, batch, cfg
 
 
+DUMP_SAMPLE = 1 << 22      # sampled elements per parameter-sized output: 2 x 16 MB of float32, under the 64 MB the dump may take
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the last timed step handed its caller — the loss it returned and the parameters and gradients it
+    left in the model — as .npy files.  Parameters and gradients (28.6 M elements each at configs[1]) are flattened in
+    `model.parameters()` order and read at one fixed, seeded set of positions, so two builds compare element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().reshape(-1) for p in params])
+    n = flat_p.numel()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(0))[:min(n, DUMP_SAMPLE)].sort().values.to(flat_p.device)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array(loss, dtype=np.float64))
+    np.save(os.path.join(out_dir, "params_sample.npy"), flat_p[idx].float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grads_sample.npy"), flat_g[idx].float().cpu().numpy())
+
+
 def other_configs_leg(args, dev, warm=6, steps=8):
     """BASELINE.json configs[2] (bf16 tensors in HBM, B=64, T_mel=1000) and configs[4] (speaker-conditioned couplings, B=48,
     T_mel=1200, 20 flow blocks, 4 speakers, gin 64): the same full training step, `warm` + `steps` steps each on fresh models,
@@ -670,6 +706,16 @@ def main():
     if reducer is not None:
         reducer.broadcast_parameters(0)
 
+    # --dump-outputs: every float atomic of a step (split-K weight gradients, parameter-gradient reductions) adds in whatever
+    # order the workgroups finish, so a step's results differ from run to run in their last bits, and a training chain
+    # compounds that (a ReLU input or an alignment decision can flip).  The state after set-up (before warm-up) is therefore
+    # kept, and the LAST timed step starts from it again (one device copy inside the timed region): the step whose outputs
+    # are written then has the same inputs in every run with the same arguments.
+    snapshot = None
+    if args.dump_outputs:
+        snapshot = [t.clone() for t in (opt._optim.flat_p, opt._optim.flat_m, opt._optim.flat_v, opt._optim.dev_state)]
+        host_state = (opt.step_num, opt.cur_lr)
+
     # single GPU: the step is captured into a hipGraph (hand-written + library kernels alike) and replayed; with a
     # process group the collectives stay outside a graph and the step is launched eagerly
     step_fn = lambda: train_batch(model, opt, batch, cfg.grad_clip, reducer)      # noqa: E731
@@ -697,8 +743,12 @@ def main():
     t0 = time.perf_counter()
     loss = None
     host_s = 0.0                                    # time the host spends queueing a step (no synchronisation inside step_fn)
-    for _ in range(args.steps):
+    for i in range(args.steps):
         h0 = time.perf_counter()
+        if snapshot is not None and i == args.steps - 1:
+            for dst, src in zip((opt._optim.flat_p, opt._optim.flat_m, opt._optim.flat_v, opt._optim.dev_state), snapshot):
+                dst.copy_(src)
+            opt.step_num, opt.cur_lr = host_state
         loss = step_fn()
         host_s += time.perf_counter() - h0
     fence()
@@ -712,6 +762,9 @@ def main():
         dt = float(tt)
     loss_val = float(loss)
     log(f"timed region: {args.steps} steps in {dt:.3f} s, loss {loss_val:.4f}")
+    if args.dump_outputs and rank == 0:              # before any leg below takes further steps on the same model
+        dump_outputs(args.dump_outputs, model, loss_val)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
     comm = None
     if reducer is not None:
         # time the compute stream spent in reducer.finish() waiting for collectives backward did not hide (HIP events on

@@ -16,6 +16,7 @@ Usage:  make -C oracle ref && python oracle/make_golden.py          (writes test
         python oracle/make_golden.py attention-long                  (only mha_c192_t240_w4 / mha_c64_t256_w4)
         python oracle/make_golden.py host                            (only the collate / table / config / checkpoint fixtures)
         python oracle/make_golden.py dropout                         (only e2e_dropout_train: a step with recorded dropout masks)
+        python oracle/make_golden.py mas-kernel                      (only mas_ref_kernel: the Cython MAS kernel called directly)
 
 This script must be run in its own process: it imports the reference under the package name `glow_tts_train`,
 which is also the name of this repo's drop-in package.
@@ -323,6 +324,27 @@ def gen_mas(R):
         arrs[f"ty{i}"] = tys
         arrs[f"path{i}"] = path
     save("mas_cases", **arrs)
+
+
+def gen_mas_kernel(R):
+    """The reference's Cython kernel called directly (maximum_path_c on pre-masked values) on seeded lattices up to the
+    benchmark's 160 x 800: what tests/test_oracle_golden.py::test_mas_oracle_vs_reference_kernel_live holds the oracle to."""
+    rng = np.random.RandomState(99)
+    arrs = {}
+    for i, (b, tx, ty) in enumerate([(4, 37, 111), (2, 160, 800), (3, 64, 64)]):
+        v = rng.randn(b, tx, ty).astype(np.float32)
+        txs = rng.randint(1, tx + 1, size=b).astype(np.int32)
+        tys = np.maximum(txs, rng.randint(1, ty + 1, size=b)).astype(np.int32)
+        txs[0], tys[0] = tx, ty
+        mask = np.zeros_like(v)
+        for j in range(b):
+            mask[j, : txs[j], : tys[j]] = 1
+        vm = (v * mask).astype(np.float32)
+        path = np.zeros_like(vm, dtype=np.int32)
+        R.core.maximum_path_c(path, vm.copy(), txs, tys)
+        arrs.update({f"value{i}": vm, f"tx{i}": txs, f"ty{i}": tys, f"path{i}": path.astype(np.int8)})
+    arrs["n"] = np.int64(3)
+    save("mas_ref_kernel", **arrs)
 
 
 def small_generator(R, gin=0, n_speakers=0, mean_only=True, n_split=4, sigmoid_scale=False):
@@ -652,8 +674,12 @@ def main():
     if sys.argv[1:] == ["dropout"]:         # only the training step with recorded dropout decisions (round 4)
         gen_e2e_dropout(R)
         return
+    if sys.argv[1:] == ["mas-kernel"]:      # only the direct-kernel MAS fixture
+        gen_mas_kernel(R)
+        return
     gen_host(R)
     gen_mas(R)
+    gen_mas_kernel(R)
     gen_flows(R)
     gen_wn_gate_squeeze(R)
     gen_attention(R)

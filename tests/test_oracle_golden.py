@@ -66,31 +66,30 @@ def test_mas_c_matches_python_loops():
 
 
 def test_mas_oracle_vs_reference_kernel_live():
-    """When oracle/_ref (the reference's own Cython kernel, built by oracle/Makefile) is present, compare live."""
+    """The oracle against the reference's own Cython kernel called directly, on seeded lattices up to 160 x 800: the kernel's
+    paths as stored in tests/golden/mas_ref_kernel.npz (oracle/make_golden.py mas-kernel) and, where oracle/_ref (built by
+    oracle/Makefile) is present, the kernel itself run live on the same inputs."""
+    g = load_golden("mas_ref_kernel")
     so = glob.glob(os.path.join(os.path.dirname(GOLDEN), "..", "oracle", "_ref", "core*.so"))
-    if not so:
-        pytest.skip("oracle/_ref not built (only possible where /root/reference exists)")
-    import importlib.machinery
-    import importlib.util
+    core = None
+    if so:
+        import importlib.machinery
+        import importlib.util
 
-    loader = importlib.machinery.ExtensionFileLoader("core", so[0])
-    spec = importlib.util.spec_from_loader("core", loader)
-    core = importlib.util.module_from_spec(spec)
-    loader.exec_module(core)
-    rng = np.random.RandomState(99)
-    for b, tx, ty in [(4, 37, 111), (2, 160, 800), (3, 64, 64)]:
-        v = rng.randn(b, tx, ty).astype(np.float32)
-        txs = rng.randint(1, tx + 1, size=b).astype(np.int32)
-        tys = np.maximum(txs, rng.randint(1, ty + 1, size=b)).astype(np.int32)
-        txs[0], tys[0] = tx, ty
-        mask = np.zeros_like(v)
-        for j in range(b):
-            mask[j, : txs[j], : tys[j]] = 1
-        vm = (v * mask).astype(np.float32)
-        want = np.zeros_like(vm, dtype=np.int32)
-        core.maximum_path_c(want, vm.copy(), txs, tys)
+        loader = importlib.machinery.ExtensionFileLoader("core", so[0])
+        spec = importlib.util.spec_from_loader("core", loader)
+        core = importlib.util.module_from_spec(spec)
+        loader.exec_module(core)
+    assert int(g["n"]) == 3
+    for i in range(int(g["n"])):
+        vm, txs, tys = g[f"value{i}"], g[f"tx{i}"], g[f"ty{i}"]
+        want = g[f"path{i}"].astype(np.int32)
+        if core is not None:
+            live = np.zeros_like(vm, dtype=np.int32)
+            core.maximum_path_c(live, vm.copy(), txs, tys)
+            assert (live == want).all(), f"case {i}: the reference kernel no longer gives the stored path"
         got = O.mas_numpy(vm, txs, tys)
-        assert (got == want).all()
+        assert (got == want).all(), f"case {i}"
 
 
 # ------------------------------------------------------------------------------------------------ flows

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print per-kernel launch times from bench.py's JSON line (roofline tables): python tools/kernel_times.py file.json [substr]"""
+"""Print per-kernel launch times from the JSON line of `bench.py --full` (roofline tables): python tools/kernel_times.py file.json [substr]"""
 import json
 import sys
 

@@ -993,6 +993,10 @@ extern "C" int glowtts_conv_fwd_io(const void *x, long x_bs, const float *wp, co
     p.y0 = static_cast<float *>(y); p.xb = io_x; p.yb = io_y;
     p.x_bs = x_bs; p.y_bs = y_bs; p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
     p.mask_in = mask_in; p.mask_out = mask_out; p.mask_add = mask_add; p.r_bs = addend_bs;
+    if (io_x == 0 && io_y == 0) {                    // the gated in-conv's backward-data in Winograd form where its U planes are bound
+        const int rc = conv_wino_bwd_dispatch(p, (hipStream_t)stream);
+        if (rc >= 0) return rc;
+    }
     return addend ? dispatch_convgemm<EPI_ADD>(p, (hipStream_t)stream) : dispatch_convgemm<EPI_PLAIN>(p, (hipStream_t)stream);
 }
 

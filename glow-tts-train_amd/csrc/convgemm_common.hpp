@@ -496,6 +496,8 @@ int conv_bf16_dispatch(ConvGemmParams &p, int epi, bool big, bool n5, bool pipe_
 
 // convwino.hip: the gated 5-tap in-conv in Winograd F(4, 5) form from U planes bound to the calling thread; -1 = not handled
 int conv_wino_gate_dispatch(ConvGemmParams &p, hipStream_t s);
+// convwino.hip: the backward-data of that conv (its packed backward weights) in the same form; -1 = not handled
+int conv_wino_bwd_dispatch(ConvGemmParams &p, hipStream_t s);
 int conv_math_forward();
 
 // convgemm_split.hip: bf16-plane arithmetic for the forward-type kernels; -1 = not handled (mode off / weights not

@@ -19,14 +19,15 @@
 // the epilogue are written as PINNED instructions in stages of independent operations (lesson 43).
 #include "convgemm_common.hpp"
 #include "split_planes.hpp"
+#include <algorithm>
 #include <atomic>
+#include <mutex>
+#include <vector>
 #include <type_traits>
 
 namespace glowtts {
 
 constexpr int WINO_P = 8;          // points
-constexpr int WINO_CB = 3;         // column blocks (16 Winograd tiles = 64 frames each) per workgroup
-constexpr int WINO_COLS = 16 * WINO_CB;
 
 // offset (bf16 elements, a multiple of 8) of the U planes of the convolution whose packed fp32 weights start `o` floats into
 // the bound buffer: sizes are multiples of 5 x 16 floats, so consecutive convolutions keep their order and never overlap
@@ -118,65 +119,197 @@ template <int J> __device__ __forceinline__ float vubyte(unsigned w) {
 }
 __device__ __forceinline__ float vhi(unsigned w) { float r; asm volatile("v_and_b32 %0, 0xffff0000, %1" : "=v"(r) : "v"(w)); return r; }
 
-// ---- the kernel ----------------------------------------------------------------------------------------------------------
-// LDS image of one 32-channel step: [plane 3][point 8][column 48][32 bf16 = 64 B], the four 16-byte chunks of a row XOR-ed
-// with (column >> 1) & 3 (a 64-byte pitch alone would put the 16 columns of a fragment read on 2 of the 8 chunk positions).
-constexpr int WINO_IMG_DW = 3 * WINO_P * WINO_COLS * 16;        // dwords per image (73 728 B)
+// AT (4 frames from the 8 points) of NW accumulator rows in LOCKSTEP, stage by stage, as pinned instructions (see vadd above)
+template <int NW>
+__device__ __forceinline__ void wino_at(const float (&m)[NW][WINO_P], float (&y)[NW][4]) {
+    float s12[NW], d12[NW], s34[NW], d34[NW], s56[NW], d56[NW], ta_[NW], tb_[NW], tc_[NW], td_[NW], te_[NW], tf_[NW], tg_[NW];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { s12[w] = vadd(m[w][1], m[w][2]); d12[w] = vsub(m[w][1], m[w][2]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { s34[w] = vadd(m[w][3], m[w][4]); d34[w] = vsub(m[w][3], m[w][4]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { s56[w] = vadd(m[w][5], m[w][6]); d56[w] = vsub(m[w][5], m[w][6]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { ta_[w] = vadd(m[w][0], s12[w]); tb_[w] = vadd(s34[w], s56[w]); tc_[w] = vmulk(2.f, d34[w]); td_[w] = vmulk(4.f, s34[w]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { te_[w] = vmulk(8.f, d34[w]); tf_[w] = vmulk(0.5f, d56[w]); tg_[w] = vmulk(0.25f, s56[w]); d56[w] = vmulk(0.125f, d56[w]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { y[w][0] = vadd(ta_[w], tb_[w]); tc_[w] = vadd(d12[w], tc_[w]); td_[w] = vadd(s12[w], td_[w]); te_[w] = vadd(d12[w], te_[w]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) { y[w][1] = vadd(tc_[w], tf_[w]); y[w][2] = vadd(td_[w], tg_[w]); te_[w] = vadd(te_[w], d56[w]); }
+#pragma unroll
+    for (int w = 0; w < NW; ++w) y[w][3] = vadd(te_[w], m[w][7]);
+}
 
-template <int EXP>
-__global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p, const unsigned short *__restrict__ U, long plane_stride) {
+// ---- the kernels -----------------------------------------------------------------------------------------------------------
+// One body, two register tiles (WinoTile): the gated forward in-conv (FWD_GATE: per wave 2 row tiles = 16 tanh + the 16 sigmoid
+// rows of the same channels x 3 column blocks; a workgroup = 128 rows x 48 Winograd tiles) and the backward-data of that conv
+// (BWD_HALF: per wave 3 row tiles x 2 column blocks; a workgroup = 192 rows x 32 Winograd tiles over ONE half of the 2H input
+// channels, the two halves combined in the launch by whichever workgroup of the pair finishes last).  Both hold 192 accumulators.
+//
+// LDS image of one 32-channel step: [plane 3][point 8][column 16 CB][32 bf16 = 64 B], the four 16-byte chunks of a row XOR-ed
+// with (column >> 1) & 3 (a 64-byte pitch alone would put the 16 columns of a fragment read on 2 of the 8 chunk positions).
+enum WinoMode { FWD_GATE = 0, BWD_HALF = 1 };
+template <int MODE> struct WinoTile {
+    static constexpr int RT = MODE == FWD_GATE ? 2 : 3;            // row tiles (16 rows) per wave
+    static constexpr int CB = MODE == FWD_GATE ? 3 : 2;            // column blocks (16 Winograd tiles = 64 frames) per workgroup
+    static constexpr int COLS = 16 * CB;
+    static constexpr int IMG_DW = 3 * WINO_P * COLS * 16;          // dwords per LDS image (73 728 / 49 152 B)
+};
+constexpr int WINO_BWD_SLOTS = 2 * 3 * 4;                          // float4 partials per lane of the backward (CB x RT x 4 rows)
+
+__device__ __forceinline__ void store4_sc1(__amdgpu_buffer_rsrc_t rs, int voff, float4 v) {      // write-through (sc1) 16-byte store
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, v), rs, voff, 0, 16);
+}
+__device__ __forceinline__ float4 load4_sc1(__amdgpu_buffer_rsrc_t rs, int voff) {               // L2-served (sc1) 16-byte load
+    return __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, 0, 16));
+}
+
+// ---- the backward's epilogue: AT, the two K halves combined by the workgroup of the pair that finishes last -----------------
+// Every workgroup stores its fp32 partial write-through (sc1, 16 B per lane: 1 KB whole lines per wave instruction) to its slot
+// of the workspace; every storing wave waits for its stores (vmcnt(0)); the workgroup meets at a barrier; ONE lane adds 1 to the
+// column group's counter (agent scope).  The workgroup whose add returns 1 came last: it loads its partner's partial with sc1
+// loads (L2-served: never a stale L1 line), adds it to its own (a + b == b + a in fp32: the result is the same whichever half
+// finished last), applies the addend and the mask, stores the output and resets the counter for the next launch.  Nobody
+// waits for anybody.  (MI355X_MICROARCH guide, the first row of the sc1 hand-off table.)
+template <int RT, int CB>
+__device__ __forceinline__ void wino_bwd_epilogue(const ConvGemmParams &p, const f32x4 (&acc)[RT][WINO_P][CB], float *ws, unsigned *cnt,
+                                                  int colg, int n_tiles, int tpu) {
+    constexpr int NW = RT * 4;                          // accumulator rows of a lane per column block: w = reg * RT + r
+    static_assert(CB * NW == WINO_BWD_SLOTS, "workspace slots");
+    __shared__ unsigned s_arrival;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lrow = lane & 15, lk = lane >> 4;
+    const int half = blockIdx.x & 1;
+    constexpr int WG_BYTES = 4 * WINO_BWD_SLOTS * 64 * 16;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(ws + (long)colg * 2 * (WG_BYTES / 4), 0, 2 * WG_BYTES, 0x00020000);
+    const int own = half * WG_BYTES + (wave * WINO_BWD_SLOTS * 64 + lane) * 16, other = (half ^ 1) * WG_BYTES + (wave * WINO_BWD_SLOTS * 64 + lane) * 16;
+    float y[CB][NW][4];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        float m[NW][WINO_P];
+#pragma unroll
+        for (int w = 0; w < NW; ++w)
+#pragma unroll
+            for (int q = 0; q < WINO_P; ++q) m[w][q] = acc[w % RT][q][cb][w / RT];
+        wino_at<NW>(m, y[cb]);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) store4_sc1(wrs, own + (cb * NW + w) * 64 * 16, make_float4(y[cb][w][0], y[cb][w][1], y[cb][w][2], y[cb][w][3]));
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (tid == 0) s_arrival = __hip_atomic_fetch_add(cnt + colg, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    GLOWTTS_TRACE_POINT(9);                             // (trace build: partials stored and the arrival counted)
+    if (s_arrival == 0) {                               // the partner is still running: it combines
+        GLOWTTS_TRACE_POINT(10);
+        return;
+    }
+    // the last of the pair: every global read first (partner's partial, addend, mask), then the arithmetic
+    float4 q[CB][NW];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb)
+#pragma unroll
+        for (int w = 0; w < NW; ++w) q[cb][w] = load4_sc1(wrs, other + (cb * NW + w) * 64 * 16);
+    const int row0 = wave * RT * 16 + lk * 4;          // row of (r, reg) = row0 + r * 16 + reg
+    float4 ad[CB][NW], mk[CB];
+    int eb[CB], et0[CB];
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        const int n = colg * 16 * CB + cb * 16 + lrow;
+        const bool ok = n < n_tiles;
+        const int b = ok ? n / tpu : 0, t0 = ok ? (n - b * tpu) * 4 : 0;     // (clamped: always a valid address)
+        eb[cb] = ok ? b : -1; et0[cb] = t0;
+        mk[cb] = p.mask_out ? *reinterpret_cast<const float4 *>(p.mask + (long)b * p.T + t0) : make_float4(1.f, 1.f, 1.f, 1.f);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const int row = row0 + (w % RT) * 16 + w / RT;
+            ad[cb][w] = p.r0 ? *reinterpret_cast<const float4 *>(p.r0 + (long)b * p.r_bs + (long)row * p.T + t0) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
+    }
+#pragma unroll
+    for (int cb = 0; cb < CB; ++cb) {
+        if (eb[cb] < 0) continue;
+        const int b = eb[cb], t0 = et0[cb];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const int row = row0 + (w % RT) * 16 + w / RT;
+            float o[4] = {y[cb][w][0] + q[cb][w].x, y[cb][w][1] + q[cb][w].y, y[cb][w][2] + q[cb][w].z, y[cb][w][3] + q[cb][w].w};
+            if (p.r0) { o[0] += ad[cb][w].x; o[1] += ad[cb][w].y; o[2] += ad[cb][w].z; o[3] += ad[cb][w].w; }
+            if (p.mask_out) { o[0] *= mk[cb].x; o[1] *= mk[cb].y; o[2] *= mk[cb].z; o[3] *= mk[cb].w; }
+            *reinterpret_cast<float4 *>(p.y0 + (long)b * p.y_bs + (long)row * p.T + t0) = make_float4(o[0], o[1], o[2], o[3]);
+        }
+    }
+    if (tid == 0) __hip_atomic_store(cnt + colg, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    GLOWTTS_TRACE_POINT(10);
+}
+
+template <int EXP, int MODE>
+__device__ __forceinline__ void wino_body(const ConvGemmParams &p, const unsigned short *__restrict__ U, long plane_stride, float *ws,
+                                          unsigned *cnt) {
+    using Tl = WinoTile<MODE>;
+    constexpr int RT = Tl::RT, WINO_CB = Tl::CB, WINO_COLS = Tl::COLS, WINO_IMG_DW = Tl::IMG_DW;
     extern __shared__ __align__(16) float smem[];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lrow = lane & 15, lk = lane >> 4;
-    const int n_rt = p.H / 64;                          // row groups: 64 tanh + 64 sigmoid rows
-    const int tile_m = blockIdx.x % n_rt;
+    const int n_rt = MODE == FWD_GATE ? p.H / 64 : 2;   // forward: row groups of 64 tanh + 64 sigmoid rows; backward: K halves
+    const int tile_m = blockIdx.x % n_rt;               // (backward: the half of the input channels)
     const int colg = blockIdx.x / n_rt;
     const int tpu = p.T >> 2;                           // Winograd tiles per utterance
     const int n_tiles = p.B * tpu;
-    const int nks = p.Cin >> 5;
+    const int nks_all = p.Cin >> 5;
+    const int nks = MODE == FWD_GATE ? nks_all : nks_all / 2;
+    const int kbase = MODE == FWD_GATE ? 0 : tile_m * nks;
 
-    f32x4 acc[2][WINO_P][WINO_CB];
+    f32x4 acc[RT][WINO_P][WINO_CB];
 #pragma unroll
-    for (int r = 0; r < 2; ++r)
+    for (int r = 0; r < RT; ++r)
 #pragma unroll
         for (int q = 0; q < WINO_P; ++q)
 #pragma unroll
             for (int c = 0; c < WINO_CB; ++c) acc[r][q][c] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     // ---- A: U planes, [point][k-step][M][32]; a lane's fragment = 16 bytes at (row, chunk lk) ------------------------------
-    const long per_point = (long)nks * p.M * 32;        // bf16 elements
+    const long per_point = (long)nks_all * p.M * 32;    // bf16 elements
     const int ubytes = (int)(WINO_P * per_point * 2);
     __amdgpu_buffer_rsrc_t urs[3];
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
         urs[pl] = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short *>(U + pl * plane_stride), 0, ubytes, 0x00020000);
-    int uvo[2];
-    uvo[0] = ((tile_m * 64 + wave * 16 + lrow) * 32 + lk * 8) * 2;                   // tanh rows
-    uvo[1] = ((p.H + tile_m * 64 + wave * 16 + lrow) * 32 + lk * 8) * 2;             // sigmoid rows of the same channels
+    int uvo[RT];
+    if constexpr (MODE == FWD_GATE) {
+        uvo[0] = ((tile_m * 64 + wave * 16 + lrow) * 32 + lk * 8) * 2;               // tanh rows
+        uvo[1] = ((p.H + tile_m * 64 + wave * 16 + lrow) * 32 + lk * 8) * 2;         // sigmoid rows of the same channels
+    } else {
+#pragma unroll
+        for (int r = 0; r < RT; ++r) uvo[r] = (((wave * RT + r) * 16 + lrow) * 32 + lk * 8) * 2;
+    }
     constexpr int RING = 4;
-    i32x4 a[RING][2][3];
+    i32x4 a[RING][RT][3];
     auto uload = [&](int q, int slot) {                 // q = k-step * 8 + point; past the end: an out-of-range offset (zeros)
         const int ks = q >> 3, pt = q & 7;
-        const int so = ks < nks ? (int)((pt * per_point + (long)ks * p.M * 32) * 2) : ubytes;
+        const int so = ks < nks ? (int)((pt * per_point + (long)(kbase + ks) * p.M * 32) * 2) : ubytes;
 #pragma unroll
-        for (int r = 0; r < 2; ++r)
+        for (int r = 0; r < RT; ++r)
 #pragma unroll
             for (int pl = 0; pl < 3; ++pl)
                 a[slot][r][pl] = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(urs[pl], uvo[r], so, 0));
     };
 
     // ---- V: three items per thread and k-step; item = (column, channel pair) ----------------------------------------------
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x), 0, (int)((long)p.B * p.x_bs * 4), 0x00020000);
+    // (backward: the resource starts at the workgroup's half of the input channels)
+    const long xoff = MODE == FWD_GATE ? 0 : (long)kbase * 32 * p.T;
+    const int xbytes = (int)(((long)p.B * p.x_bs - xoff) * 4);
+    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.x + xoff), 0, xbytes, 0x00020000);
     constexpr int OOR = 0x7ffffff0;
-    int voL[3], voM[3], voR[3], sdw[3];
-    bool hasL[3], hasR[3];
+    int voL[WINO_CB], voM[WINO_CB], voR[WINO_CB], sdw[WINO_CB];
+    bool hasL[WINO_CB], hasR[WINO_CB];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < WINO_CB; ++i) {
         // lanes: 16 consecutive columns x 4 channel pairs — a 16-byte load instruction covers 4 (x 2) channel rows of 256
         // contiguous bytes (with the channel pair fastest it was 16 rows of 64 bytes, and the input loads cost the kernel 10 us:
         // the texture path works per cache line touched)
         const int idx = tid + 256 * i;
         const int r12 = idx >> 6;
-        const int col = (r12 % 3) * 16 + (idx & 15), cp = (r12 / 3) * 4 + ((idx >> 4) & 3);
+        const int col = (r12 % WINO_CB) * 16 + (idx & 15), cp = (r12 / WINO_CB) * 4 + ((idx >> 4) & 3);
         const int n = colg * WINO_COLS + col;
         const int b = n / tpu, t0 = (n - b * tpu) * 4;
         const int gsel = cp >> 3, kk = 2 * (cp & 7);
@@ -192,9 +325,8 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
         sdw[i] = col * 16 + (((kk >> 2) ^ ((col >> 1) & 3)) * 4) + gsel * 2 + (cp & 1);
     }
     const int rowb = p.T * 4;
-    float xr[3][2][8];
+    float xr[WINO_CB][2][8];
     float dmy[6] = {1.f, 2.f, 3.f, 4.f, 5.f, 6.f}, dsc = 0.999f + 1e-6f * lane;
-    const int xbytes = (int)((long)p.B * p.x_bs * 4);
     auto xload1 = [&](int ks, int i) {
         const int so = ks < nks ? ks * 32 * rowb : xbytes;        // past the last step: out of range (zeros, no memory access)
 #pragma unroll
@@ -229,35 +361,37 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
     GLOWTTS_TRACE_POINT(0);
 #pragma unroll
     for (int i = 0; i < RING - 1; ++i) uload(i, i);
-    xload1(0, 0); xload1(0, 1); xload1(0, 2);
-    {   // the first image: the thread's six channels (3 items x 2) transformed in LOCKSTEP and the 24 (item, point) pairs split in
-        // lockstep, as pinned instructions (the compiler's order for this — one value chain after the other — took 2.4 us)
-        float pv[3][2][WINO_P];
 #pragma unroll
-        for (int i = 0; i < 3; ++i) { xhalo(i, 0); xhalo(i, 1); }
-        float a0[6], a1[6], a2[6], a3[6], a4[6], a5[6], m0[6], m1[6], m2[6], m3[6], m4[6], m5[6], u0[6], u1[6], u2[6], u3[6];
+    for (int i = 0; i < WINO_CB; ++i) xload1(0, i);
+    {   // the first image: the thread's channels (2 per item) transformed in LOCKSTEP and the (item, point) pairs split in
+        // lockstep, as pinned instructions (the compiler's order for this — one value chain after the other — took 2.4 us)
+        constexpr int NW = 2 * WINO_CB;
+        float pv[WINO_CB][2][WINO_P];
+#pragma unroll
+        for (int i = 0; i < WINO_CB; ++i) { xhalo(i, 0); xhalo(i, 1); }
+        float a0[NW], a1[NW], a2[NW], a3[NW], a4[NW], a5[NW], m0[NW], m1[NW], m2[NW], m3[NW], m4[NW], m5[NW], u0[NW], u1[NW], u2[NW], u3[NW];
 #define WD(j) xr[w >> 1][w & 1][j]
 #define WV(j) pv[w >> 1][w & 1][j]
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { a0[w] = vsub(WD(6), WD(0)); a1[w] = vsub(WD(2), WD(4)); a2[w] = vsub(WD(7), WD(1)); a3[w] = vsub(WD(3), WD(5)); a4[w] = vadd(WD(2), WD(6)); a5[w] = vadd(WD(1), WD(5)); }
+        for (int w = 0; w < NW; ++w) { a0[w] = vsub(WD(6), WD(0)); a1[w] = vsub(WD(2), WD(4)); a2[w] = vsub(WD(7), WD(1)); a3[w] = vsub(WD(3), WD(5)); a4[w] = vadd(WD(2), WD(6)); a5[w] = vadd(WD(1), WD(5)); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { m0[w] = vmulk(5.25f, a1[w]); m1[w] = vmulk(5.25f, a3[w]); m2[w] = vmulk(4.25f, WD(4)); m3[w] = vmulk(4.25f, WD(3)); m4[w] = vmulk(0.25f, WD(2)); m5[w] = vmulk(1.25f, WD(4)); }
+        for (int w = 0; w < NW; ++w) { m0[w] = vmulk(5.25f, a1[w]); m1[w] = vmulk(5.25f, a3[w]); m2[w] = vmulk(4.25f, WD(4)); m3[w] = vmulk(4.25f, WD(3)); m4[w] = vmulk(0.25f, WD(2)); m5[w] = vmulk(1.25f, WD(4)); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { WV(0) = vadd(a0[w], m0[w]); WV(7) = vadd(a2[w], m1[w]); u0[w] = vsub(a4[w], m2[w]); u1[w] = vsub(a5[w], m3[w]); u2[w] = vadd(WD(6), m4[w]); m0[w] = vmulk(0.5f, WD(1)); }
+        for (int w = 0; w < NW; ++w) { WV(0) = vadd(a0[w], m0[w]); WV(7) = vadd(a2[w], m1[w]); u0[w] = vsub(a4[w], m2[w]); u1[w] = vsub(a5[w], m3[w]); u2[w] = vadd(WD(6), m4[w]); m0[w] = vmulk(0.5f, WD(1)); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { WV(1) = vadd(u0[w], u1[w]); WV(2) = vsub(u0[w], u1[w]); u3[w] = vsub(u2[w], m5[w]); m1[w] = vmulk(2.5f, WD(3)); m2[w] = vmulk(2.f, WD(5)); m3[w] = vmulk(4.f, WD(2)); }
+        for (int w = 0; w < NW; ++w) { WV(1) = vadd(u0[w], u1[w]); WV(2) = vsub(u0[w], u1[w]); u3[w] = vsub(u2[w], m5[w]); m1[w] = vmulk(2.5f, WD(3)); m2[w] = vmulk(2.f, WD(5)); m3[w] = vmulk(4.f, WD(2)); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { a0[w] = vsub(m0[w], m1[w]); a1[w] = vadd(WD(6), m3[w]); m4[w] = vmulk(5.f, WD(4)); m5[w] = vmulk(2.f, WD(1)); m0[w] = vmulk(0.5f, WD(5)); }
+        for (int w = 0; w < NW; ++w) { a0[w] = vsub(m0[w], m1[w]); a1[w] = vadd(WD(6), m3[w]); m4[w] = vmulk(5.f, WD(4)); m5[w] = vmulk(2.f, WD(1)); m0[w] = vmulk(0.5f, WD(5)); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { u0[w] = vadd(a0[w], m2[w]); u1[w] = vsub(a1[w], m4[w]); a2[w] = vsub(m5[w], m1[w]); }
+        for (int w = 0; w < NW; ++w) { u0[w] = vadd(a0[w], m2[w]); u1[w] = vsub(a1[w], m4[w]); a2[w] = vsub(m5[w], m1[w]); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { WV(3) = vadd(u3[w], u0[w]); WV(4) = vsub(u3[w], u0[w]); a3[w] = vadd(a2[w], m0[w]); }
+        for (int w = 0; w < NW; ++w) { WV(3) = vadd(u3[w], u0[w]); WV(4) = vsub(u3[w], u0[w]); a3[w] = vadd(a2[w], m0[w]); }
 #pragma unroll
-        for (int w = 0; w < 6; ++w) { WV(5) = vadd(u1[w], a3[w]); WV(6) = vsub(u1[w], a3[w]); }
+        for (int w = 0; w < NW; ++w) { WV(5) = vadd(u1[w], a3[w]); WV(6) = vsub(u1[w], a3[w]); }
 #undef WD
 #undef WV
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {                   // eight points of an item in lockstep
+        for (int i = 0; i < WINO_CB; ++i) {             // eight points of an item in lockstep
             float sa[WINO_P], sb[WINO_P], lo[WINO_P], hi[WINO_P];
             unsigned sw[3][WINO_P];
 #pragma unroll
@@ -280,7 +414,8 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
                 for (int k = 0; k < 3; ++k) dst[(k * WINO_P + q) * (WINO_COLS * 16)] = sw[k][q];
         }
     }
-    xload1(1, 0); xload1(1, 1); xload1(1, 2);
+#pragma unroll
+    for (int i = 0; i < WINO_CB; ++i) xload1(1, i);
     lds_barrier();
     GLOWTTS_TRACE_POINT(1);
     // One k-step.  MORE (compile time): the next step's image is made beside the MFMAs; loads past the last step use an
@@ -289,11 +424,11 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
     // One wave per SIMD means nobody else fills a stall: a vector instruction that needs the result of the one before it waits
     // ~8 cycles, and the compiler orders the transform / split arithmetic for few registers, i.e. as dependent chains (measured:
     // the staging arithmetic cost the same 10 us per launch wherever the scheduler put it).  So the order is pinned here: a region
-    // = one (point, column block) = six MFMA PAIRS (one product each for the tanh and the sigmoid row tile), and behind every
-    // pair ONE STAGE of the staging work — up to six vector instructions that are independent of each other and whose inputs
-    // were produced a whole pair (32 cycles) earlier.  24 regions per step; item i of the thread's three takes regions
-    // 8 i .. 8 i + 7: its two channels' transforms (regions 0, 1), its eight points split three at a time in lockstep and stored
-    // (regions 2, 4, 6), then its registers take the step after next.
+    // = one (point, column block) = six MFMA GROUPS (one product per row tile: the tanh and the sigmoid tile, or the backward's
+    // three), and behind every group ONE STAGE of the staging work — up to six vector instructions that are independent of each
+    // other and whose inputs were produced a whole group (32 cycles or more) earlier.  8 CB regions per step; item i of the
+    // thread's CB takes regions 8 i .. 8 i + 7: its two channels' transforms (regions 0, 1), its eight points split three at a
+    // time in lockstep and stored (regions 2, 4, 6), then its registers take the step after next.
     auto kstep = [&](int ks, auto more_tag) {
         constexpr bool MORE = decltype(more_tag)::value && EXP != 3;
         const float *cur = smem + (ks & 1) * WINO_IMG_DW;
@@ -361,7 +496,7 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
                 for (int k = 0; k < 6; ++k) {
                     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                    for (int r = 0; r < 2; ++r)
+                    for (int r = 0; r < RT; ++r)
                         acc[r][pt][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
                             __builtin_bit_cast(bf16x8, a[pt % RING][r][product_a(3, k)]),
                             __builtin_bit_cast(bf16x8, bv[n & 1][product_b(3, k)]), acc[r][pt][cb], 0, 0, 0);
@@ -394,7 +529,10 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
     for (int ks = 0; ks + 1 < nks; ++ks) kstep(ks, std::true_type{});
     kstep(nks - 1, std::false_type{});
     GLOWTTS_TRACE_POINT(8);
-
+    if constexpr (MODE == BWD_HALF) {
+        wino_bwd_epilogue<RT, WINO_CB>(p, acc, ws, cnt, colg, n_tiles, tpu);
+        return;
+    } else {
     // ---- output transform (AT) in registers, then the gate (utils.py:31-38) and the stores ------------------------------------
     // acc[r][pt][cb][reg]: row lk * 4 + reg of the wave's tanh (r = 0) / sigmoid (r = 1) tile, Winograd tile cb * 16 + lrow.
     // Every global read of the epilogue (keep bytes, biases, conditioning rows) is issued FIRST: one wave per SIMD would otherwise
@@ -437,27 +575,12 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
         const int b = eb[cb], t0 = et0[cb];
         float y[8][4];                                   // row = reg * 2 + r
         {
-            float m[8][WINO_P], s12[8], d12[8], s34[8], d34[8], s56[8], d56[8], ta_[8], tb_[8], tc_[8], td_[8], te_[8], tf_[8], tg_[8];
+            float m[8][WINO_P];
 #pragma unroll
             for (int w = 0; w < 8; ++w)
 #pragma unroll
                 for (int q = 0; q < WINO_P; ++q) m[w][q] = acc[w & 1][q][cb][w >> 1];
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { s12[w] = vadd(m[w][1], m[w][2]); d12[w] = vsub(m[w][1], m[w][2]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { s34[w] = vadd(m[w][3], m[w][4]); d34[w] = vsub(m[w][3], m[w][4]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { s56[w] = vadd(m[w][5], m[w][6]); d56[w] = vsub(m[w][5], m[w][6]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { ta_[w] = vadd(m[w][0], s12[w]); tb_[w] = vadd(s34[w], s56[w]); tc_[w] = vmulk(2.f, d34[w]); td_[w] = vmulk(4.f, s34[w]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { te_[w] = vmulk(8.f, d34[w]); tf_[w] = vmulk(0.5f, d56[w]); tg_[w] = vmulk(0.25f, s56[w]); d56[w] = vmulk(0.125f, d56[w]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { y[w][0] = vadd(ta_[w], tb_[w]); tc_[w] = vadd(d12[w], tc_[w]); td_[w] = vadd(s12[w], td_[w]); te_[w] = vadd(d12[w], te_[w]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) { y[w][1] = vadd(tc_[w], tf_[w]); y[w][2] = vadd(td_[w], tg_[w]); te_[w] = vadd(te_[w], d56[w]); }
-#pragma unroll
-            for (int w = 0; w < 8; ++w) y[w][3] = vadd(te_[w], m[w][7]);
+            wino_at<8>(m, y);
         }
 #pragma unroll
         for (int w = 0; w < 8; ++w)
@@ -519,6 +642,19 @@ __global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p,
     }
     if (EXP == 7 && dmy[0] + dmy[1] + dmy[2] + dmy[3] + dmy[4] + dmy[5] == 1234.5f) p.y0[0] = 0.f;
     GLOWTTS_TRACE_POINT(10);
+    }
+}
+
+template <int EXP>
+__global__ __launch_bounds__(256, 1) void wino_gate_fwd_kernel(ConvGemmParams p, const unsigned short *__restrict__ U, long plane_stride) {
+    wino_body<EXP, FWD_GATE>(p, U, plane_stride, nullptr, nullptr);
+}
+
+// backward-data of the gated in-conv (EPI_ADD / EPI_PLAIN, optional mask_out): workgroup 2 c + h = column group c, input channels
+// [h Cin / 2, (h + 1) Cin / 2); ws = 2 x (partials of a workgroup) per column group, cnt = one arrival counter per column group
+__global__ __launch_bounds__(256, 1) void wino_bwd_kernel(ConvGemmParams p, const unsigned short *__restrict__ U, long plane_stride,
+                                                          float *ws, unsigned *cnt) {
+    wino_body<0, BWD_HALF>(p, U, plane_stride, ws, cnt);
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
@@ -540,10 +676,11 @@ int conv_wino_gate_dispatch(ConvGemmParams &p, hipStream_t s) {
     if (p.H % 64 != 0 || p.Cin % 32 != 0 || p.M != 2 * p.H || p.T % 4 != 0) return -1;
     if (!aligned16(p.x) || !aligned16(p.y0) || !aligned16(p.y1) || !aligned16(p.drop) || (long)p.B * p.x_bs * 4 >= 0x7ffffff0L) return -1;
     const unsigned short *U = w.planes + wino_u_offset(p.wp - w.wp);
-    const size_t lds = (size_t)2 * WINO_IMG_DW * sizeof(float);
+    const size_t lds = (size_t)2 * WinoTile<FWD_GATE>::IMG_DW * sizeof(float);
     static LdsLimit attr_max_e;
     if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&wino_gate_fwd_kernel<0>), lds, "glowtts_conv_gate_fwd (Winograd)")) return rc_;
     const int n_tiles = p.B * (p.T / 4);
+    constexpr int WINO_COLS = WinoTile<FWD_GATE>::COLS;
     dim3 grid((unsigned)(((n_tiles + WINO_COLS - 1) / WINO_COLS) * (p.H / 64)));
 #ifdef GLOWTTS_TRACE
     // timing experiments of the tuning build (tools/wino_bench.py; results WRONG): GLOWTTS_WINO = 1 + 2 x {1: no split / store of the
@@ -568,11 +705,89 @@ int conv_wino_gate_dispatch(ConvGemmParams &p, hipStream_t s) {
     GLOWTTS_LAUNCH_CHECK("glowtts_conv_gate_fwd (Winograd)");
 }
 
+// Workspace of the backward kernel: per (device, stream) — two eager launches on different streams never share partials or
+// counters.  Allocated with hipMalloc at the stream's first launch (grown when a larger shape comes), counters zeroed at allocation;
+// every launch leaves its counters at zero again.  Never allocated while the stream is being captured into a graph: a launch
+// captured on a stream without a workspace takes the direct kernel.  A captured launch keeps the workspace it found, so a buffer
+// that a larger shape outgrew is RETIRED, never freed (a graph may still point at it), and the workspaces live as long as the
+// process.  Restriction: a graph that captured this kernel must not be replayed concurrently with eager launches on its capture
+// stream (or with another replay of itself): they would share one workspace.
+struct WinoBwdWorkspace {
+    int dev;
+    hipStream_t stream;
+    float *partials;
+    unsigned *counters;
+    long n_groups;             // column groups the allocation holds
+};
+static std::mutex g_wino_ws_mu;
+static std::vector<WinoBwdWorkspace> g_wino_ws;
+static std::atomic<long> g_wino_bwd_launches{0};
+
+static int wino_bwd_workspace(hipStream_t s, long n_groups, float **partials, unsigned *&counters) {
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lock(g_wino_ws_mu);
+    WinoBwdWorkspace *e = nullptr;
+    for (auto &w : g_wino_ws)
+        if (w.dev == dev && w.stream == s) e = &w;
+    if (e && e->n_groups >= n_groups) { *partials = e->partials; counters = e->counters; return 0; }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return -1;
+    if (e) n_groups = std::max(n_groups, 2 * e->n_groups);      // (at least doubled: the retired buffers stay below the live one)
+    const size_t part_bytes = (size_t)n_groups * 2 * 4 * WINO_BWD_SLOTS * 64 * 16;
+    void *mem = nullptr;
+    if (hipMalloc(&mem, part_bytes + (size_t)n_groups * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    if (hipMemsetAsync(static_cast<char *>(mem) + part_bytes, 0, (size_t)n_groups * sizeof(unsigned), s) != hipSuccess) {
+        (void)hipFree(mem);
+        return -1;
+    }
+    if (!e) {                                           // (a grown-out buffer stays allocated: queued launches or graphs use it)
+        g_wino_ws.push_back(WinoBwdWorkspace{dev, s, nullptr, nullptr, 0});
+        e = &g_wino_ws.back();
+    }
+    e->partials = static_cast<float *>(mem);
+    e->counters = reinterpret_cast<unsigned *>(static_cast<char *>(mem) + part_bytes);
+    e->n_groups = n_groups;
+    *partials = e->partials;
+    counters = e->counters;
+    return 0;
+}
+
+// -1 = not handled: the backward-data of the gated in-conv (the in-conv's packed backward weights, M rows, Cin = 2 M input
+// channels, 5 taps, pad 2) in Winograd form where its U planes are bound, the switch GLOWTTS_WINO_BWD is on and the shape fits
+int conv_wino_bwd_dispatch(ConvGemmParams &p, hipStream_t s) {
+    if (!knob(K_WINO_BWD) || conv_math_forward() != 3) return -1;
+    const WinoBinding &w = t_wino;
+    if (w.wp == nullptr || p.wp < w.wp || p.wp >= w.wp + w.n) return -1;
+    if (p.taps != 5 || p.dil != 1 || p.pad != 2 || p.xb || p.yb || p.x2 || p.mask_in || p.mask_add || p.bias || p.relu || p.drop ||
+        p.gate_pos)
+        return -1;
+    if (p.M != 192 || p.Cin != 2 * p.M || p.T % 4 != 0) return -1;
+    if (!aligned16(p.x) || !aligned16(p.y0) || !aligned16(p.r0) || (p.mask_out && !aligned16(p.mask)) || p.x_bs % 4 || p.y_bs % 4 ||
+        (p.r0 && p.r_bs % 4) || (long)p.B * p.x_bs * 4 >= 0x7ffffff0L)
+        return -1;
+    const int n_tiles = p.B * (p.T / 4);
+    constexpr int COLS = WinoTile<BWD_HALF>::COLS;
+    const long n_groups = (n_tiles + COLS - 1) / COLS;
+    float *ws = nullptr;
+    unsigned *cnt = nullptr;
+    if (wino_bwd_workspace(s, n_groups, &ws, cnt) != 0) return -1;
+    const unsigned short *U = w.planes + wino_u_offset(p.wp - w.wp);
+    const size_t lds = (size_t)2 * WinoTile<BWD_HALF>::IMG_DW * sizeof(float);
+    static LdsLimit attr_max_b;
+    if (int rc_ = attr_max_b.ensure(reinterpret_cast<const void *>(&wino_bwd_kernel), lds, "glowtts_conv_fwd (Winograd backward-data)")) return rc_;
+    g_wino_bwd_launches.fetch_add(1, std::memory_order_relaxed);
+    hipLaunchKernelGGL(wino_bwd_kernel, dim3((unsigned)(2 * n_groups)), dim3(256), lds, s, p, U, w.stride, ws, cnt);
+    GLOWTTS_LAUNCH_CHECK("glowtts_conv_fwd (Winograd backward-data)");
+}
+
 }  // namespace glowtts
 
 using namespace glowtts;
 
 extern "C" long glowtts_wino_launches(void) { return g_wino_launches.load(std::memory_order_relaxed); }
+
+extern "C" long glowtts_wino_bwd_launches(void) { return g_wino_bwd_launches.load(std::memory_order_relaxed); }
 
 extern "C" long glowtts_wino_plane_elems(long n) { return wino_u_offset(n) + 8; }
 

@@ -161,7 +161,8 @@ class EncLayer(ctypes.Structure):
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["glowtts_last_error", "glowtts_abi_version", "glowtts_conv_math",
                            "glowtts_conv_bind_planes", "glowtts_conv_bind_planes_ns", "glowtts_wn_fused",
                            "glowtts_set_knob", "glowtts_get_knob", "glowtts_mas_spans_supported",
-                           "glowtts_conv_bind_wino", "glowtts_wino_plane_elems", "glowtts_wino_launches"])
+                           "glowtts_conv_bind_wino", "glowtts_wino_plane_elems", "glowtts_wino_launches",
+                           "glowtts_wino_bwd_launches"])
 
 _lib: Optional[ctypes.CDLL] = None
 _fn_cache: dict = {}
@@ -210,6 +211,8 @@ def load() -> ctypes.CDLL:
     lib.glowtts_wino_plane_elems.argtypes = [_L]
     lib.glowtts_wino_launches.restype = _L
     lib.glowtts_wino_launches.argtypes = []
+    lib.glowtts_wino_bwd_launches.restype = _L
+    lib.glowtts_wino_bwd_launches.argtypes = []
     for name, args in _SIGNATURES.items():
         fn = getattr(lib, name)
         fn.restype = _I
@@ -321,6 +324,11 @@ def conv_bind_planes(wp: Optional[torch.Tensor], planes: Optional[torch.Tensor] 
 def wino_launches() -> int:
     """Launches of the Winograd form of the gated in-conv (csrc/convwino.hip) by this process so far."""
     return int(load().glowtts_wino_launches())
+
+
+def wino_bwd_launches() -> int:
+    """Launches of the Winograd form of the gated in-conv's backward-data (csrc/convwino.hip) by this process so far."""
+    return int(load().glowtts_wino_bwd_launches())
 
 
 def wino_plane_elems(n: int) -> int:

@@ -498,10 +498,12 @@ class WNPackPlan:
             arena, planes = self._plane_home(True)
             call("glowtts_pack_weight_planes_multi", ptr(self.desc), ptr(self.prefix), len(self.convs), self.total_rows,
                  ptr(arena), arena.numel(), ptr(planes))
-            if self.shared is None and self.wino and _WINO and _hip.get_knob("WINO"):
+            if self.shared is None and self.wino:
                 _wino_update(self, arena, [self])     # (a block with its own packed buffer: the per-block path, e.g. configs[4])
         else:
             call("glowtts_pack_weight_multi", ptr(self.desc), ptr(self.prefix), len(self.convs), self.total_rows)
+            if self.shared is None:
+                self.wino_fresh = (False, False)      # (Winograd-domain planes, if any, are of older weights now)
 
     def bind(self) -> bool:
         """Hand this stack's planes to the calling thread's next convolution launches (no-op in native fp32 mode)."""
@@ -511,8 +513,8 @@ class WNPackPlan:
                 conv_bind_planes(arena, planes)
                 owner = self.shared if self.shared is not None else self
                 wino = getattr(owner, "wino_planes", None)
-                if wino is not None and getattr(owner, "wino_key", None) is arena:
-                    _hip.conv_bind_wino(arena, wino)     # (used by the gated in-conv while the switch GLOWTTS_WINO is on)
+                if wino is not None and getattr(owner, "wino_key", None) is arena and _wino_current(owner):
+                    _hip.conv_bind_wino(arena, wino)     # (the gated in-conv / its backward-data under GLOWTTS_WINO / _WINO_BWD)
                 return True
         return False
 
@@ -613,10 +615,10 @@ class StackArena:
         if _SPLIT_MATH[0] and plans[0].want_planes:
             call("glowtts_pack_weight_planes_multi", ptr(self.desc), ptr(self.prefix), self.n_conv, self.total_rows, ptr(self.arena),
                  self.arena.numel(), ptr(self.planes_buffer(True)))
-            if _WINO and _hip.get_knob("WINO"):
-                self.wino_weights(plans)
+            self.wino_weights(plans)
         else:
             call("glowtts_pack_weight_multi", ptr(self.desc), ptr(self.prefix), self.n_conv, self.total_rows)
+            self.wino_fresh = (False, False)          # (Winograd-domain planes, if any, are of older weights now)
 
     def wino_weights(self, plans):
         """Winograd-domain planes (csrc/convwino.hip) of every gated 5-tap in-conv of the stack: one launch behind the weight pack."""
@@ -624,21 +626,47 @@ class StackArena:
 
 
 def _wino_update(owner, arena, plans):
-    """(Re)make the Winograd-domain planes of the gated 5-tap in-convs packed in `arena` (a flow stack's buffer or one block's own):
-    table of (offset, Cin / 16, M) rows built once per buffer, one `glowtts_wino_weights` launch per packing."""
+    """(Re)make the Winograd-domain planes of the gated 5-tap in-convs packed in `arena` (a flow stack's buffer or one block's own)
+    after a packing: the forward packs while GLOWTTS_WINO is on, the backward-data packs (in-convs of 192 channels, the only width
+    the backward-data kernel takes) while GLOWTTS_WINO_BWD is on.  Table of (offset, Cin / 16, M) rows built once per buffer
+    (forward rows first, then backward rows), one `glowtts_wino_weights` launch over the rows wanted.  `owner.wino_fresh` records
+    which of the two sets match the packed weights: `bind` hands the planes out only where every switched-on form has fresh ones."""
+    want_f = bool(_WINO and _hip.get_knob("WINO"))
+    want_b = bool(_hip.get_knob("WINO_BWD"))
+    if not (want_f or want_b):
+        owner.wino_fresh = (False, False)
+        return
     if getattr(owner, "wino_key", None) is not arena:
-        rows = []
+        fwd, bwd = [], []
         for p in plans:
-            for (_v, _g, wp_f, _b, _inv, cout, cin, taps, _off) in p.convs:
+            for (_v, _g, wp_f, wp_b, _inv, cout, cin, taps, _off) in p.convs:
                 if taps == 5 and cout == 2 * cin and cin % 64 == 0:
-                    rows.append([(wp_f.data_ptr() - arena.data_ptr()) // 4, cin // 16, cout])
+                    fwd.append([(wp_f.data_ptr() - arena.data_ptr()) // 4, cin // 16, cout])
+                    if cin == 192:      # its backward-data weights (right behind, already tap-flipped, same layout)
+                        bwd.append([(wp_b.data_ptr() - arena.data_ptr()) // 4, cout // 16, cin])
+        rows = fwd + bwd
         owner.wino_table = torch.tensor(rows, dtype=torch.int64).to(arena.device) if rows else None
+        owner.wino_nf = len(fwd)
         owner.wino_planes = (torch.zeros(3 * _hip.wino_plane_elems(arena.numel()), device=arena.device, dtype=torch.int16)
                              if rows else None)
         owner.wino_key = arena
-    if owner.wino_table is not None:
-        call("glowtts_wino_weights", ptr(arena), arena.numel(), ptr(owner.wino_table), owner.wino_table.shape[0],
+    owner.wino_fresh = (False, False)
+    if owner.wino_table is None:
+        return
+    n = owner.wino_table.shape[0]
+    lo = 0 if want_f else owner.wino_nf
+    hi = n if want_b else owner.wino_nf
+    if hi > lo:
+        call("glowtts_wino_weights", ptr(arena), arena.numel(), ptr(owner.wino_table[lo:hi]), hi - lo,
              ptr(owner.wino_planes), owner.wino_planes.numel() // 3)
+    owner.wino_fresh = (want_f, want_b)
+
+
+def _wino_current(owner) -> bool:
+    """Do the owner's Winograd-domain planes match its packed weights for every form whose switch is on now?  (A switch flipped on
+    after the packing finds planes of older weights: the planes are then not bound, and the direct kernels run.)"""
+    fresh_f, fresh_b = getattr(owner, "wino_fresh", (False, False))
+    return ((fresh_f or not _hip.get_knob("WINO")) and (fresh_b or not _hip.get_knob("WINO_BWD"))) and (fresh_f or fresh_b)
 
 
 # The gated 5-tap in-conv of the flow stack in its Winograd F(4, 5) form (csrc/convwino.hip, DESIGN.md 4k): 35.4 us against 48.4 for the

@@ -35,6 +35,10 @@
  *                                                     (csrc/convwino.hip) wherever Winograd-domain planes are bound to the launching
  *                                                     thread (glowtts_conv_bind_wino); results differ from the direct form by the
  *                                                     fp32 roundings of the transforms (same tolerance against the oracle)
+ *                                 GLOWTTS_WINO_BWD    [1]     1 = the backward-data of that conv (glowtts_conv_fwd with its packed backward
+ *                                                     weights: M = 192 rows, 2M input channels, 5 taps, pad 2, T % 4 == 0, optional
+ *                                                     addend and mask_out) in the same Winograd form where its planes are bound,
+ *                                                     the two halves of the input channels combined inside the launch
  *                                 GLOWTTS_WRW1_MULTI  [1]     0 = the 1x1 weight gradients of a flow block / transformer layer as separate
  *                                                     launches instead of one multi-problem launch (csrc/convwrw1.hip)
  *                                 GLOWTTS_WRW1_CUS    [-1]    compute units the multi-problem 1x1 weight gradient sizes its split-K for
@@ -603,12 +607,19 @@ int glowtts_conv_bind_planes_ns(const float *wp, long n_floats, const uint16_t *
  * form needs 20.  U and V are fp32 values, each split into three bf16 planes (six products per fp32 product, fp32 accumulation).
  *   wino_plane_elems(n) : bf16 elements per plane of the U planes of a packed-weight buffer of n floats
  *   wino_weights : U planes of the listed convolutions of a packed buffer; table (device, int64) rows = (offset of the convolution's
- *       packed FORWARD weights in floats, Cin / 16, M); planes = 3 x plane_stride bf16 (caller's memory); after every packing
+ *       packed weights in floats, Cin / 16, M) — a gated in-conv's forward pack and its backward pack (tap-flipped, Cin = 2H,
+ *       M = H); planes = 3 x plane_stride bf16 (caller's memory); after every packing
  *   conv_bind_wino : bind (wp = NULL: unbind) those planes to the calling thread; glowtts_conv_gate_fwd then takes the
  *       Winograd kernel when GLOWTTS_WINO = 1, arithmetic mode bf16x6, fp32 tensors, 5 taps, dilation 1, H % 64 == 0, T % 4 == 0,
- *       16-byte-aligned tensors — and the direct kernels otherwise. */
+ *       16-byte-aligned tensors — and the direct kernels otherwise; glowtts_conv_fwd with the backward pack takes the Winograd
+ *       backward-data kernel when GLOWTTS_WINO_BWD = 1 and the shape fits (see that switch), also the direct kernel otherwise.
+ *       That kernel keeps a workspace per (device, stream) (hipMalloc outside any caller's allocator), allocated at its first
+ *       launch on the stream and grown at least twofold for a larger shape, never during a graph capture (the direct kernel runs
+ *       then), never freed (a captured graph may hold it); a graph that captured it must not be replayed concurrently with eager
+ *       launches on its capture stream.  The caller binds planes made from the CURRENT packed weights only. */
 long glowtts_wino_plane_elems(long n_floats);
 long glowtts_wino_launches(void);        /* launches of the Winograd kernel by this process so far (tests, bench.py) */
+long glowtts_wino_bwd_launches(void);    /* launches of the Winograd backward-data kernel by this process so far */
 int glowtts_wino_weights(const float *wp, long n_floats, const long *table, int n_conv, uint16_t *planes, long plane_stride,
                          glowtts_stream_t stream);
 int glowtts_conv_bind_wino(const float *wp, long n_floats, const uint16_t *planes, long plane_stride);

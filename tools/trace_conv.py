@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Phase timeline of one conv-kernel launch (tuning tool; needs the trace build: `make -C glow-tts-train_amd/csrc trace`).
-Usage: GLOWTTS_HIP_LIB=tools/libglowtts_trace.bin python tools/trace_conv.py [gate|resskip|bwd_data5|bwd_data1|start]"""
+Usage: GLOWTTS_HIP_LIB=tools/libglowtts_trace.bin python tools/trace_conv.py [gate|resskip|bwd_data5|bwd_data1|start|wino|wino_bwd]"""
 import ctypes
 import os
 import sys
@@ -55,6 +55,9 @@ if which == "wrw5p":                                   # weight gradient from op
 if which == "wino":                                    # the gated in-conv in its Winograd form (csrc/convwino.hip)
     fns["wino"] = fns["gate"]
     os.environ.setdefault("TRACE_CONV_MATH", "bf16x6+wrw")
+if which == "wino_bwd":                                # the in-conv's backward-data in Winograd form (csrc/convwino.hip: wino_bwd_kernel)
+    fns["wino_bwd"] = fns["bwd_data5"]
+    os.environ.setdefault("TRACE_CONV_MATH", "bf16x6+wrw")
 fn = fns[which]
 lib = _hip.load()
 split = os.environ.get("TRACE_CONV_MATH")          # e.g. "bf16x6+wrw": trace the bf16-plane kernels (convgemm_split.hip)
@@ -63,7 +66,7 @@ if split:
     _planes = {}
     for w in (wf_in, wb_in, wf_rs, wb_rs):          # bind the one buffer the chosen kernel uses
         _planes[w.data_ptr()] = torch.empty(3 * w.numel(), device=dev, dtype=torch.int16)
-    _use = {"gate": wf_in, "wino": wf_in, "resskip": wf_rs, "bwd_data5": wb_in, "bwd_data1": wb_rs, "gate_bwd": wb_rs}.get(which)
+    _use = {"gate": wf_in, "wino": wf_in, "wino_bwd": wb_in, "resskip": wf_rs, "bwd_data5": wb_in, "bwd_data1": wb_rs, "gate_bwd": wb_rs}.get(which)
     if _use is not None:
         call("glowtts_conv_split_weights", ptr(_use), _use.numel(), ptr(_planes[_use.data_ptr()]))
         _hip.conv_bind_planes(_use, _planes[_use.data_ptr()])
@@ -75,6 +78,14 @@ if which == "wino":
     call("glowtts_wino_weights", ptr(wf_in), wf_in.numel(), ptr(table), 1, ptr(u_planes), n_u)
     _hip.conv_bind_wino(wf_in, u_planes)
     _hip.set_knob("WINO", 1)
+    rd = lib.glowtts_debug_trace_read_wino
+if which == "wino_bwd":        # trace points: 0 start, 1 first image staged, 2-7 end of k-steps 0-5, 8 loop done, 9 partial stored and counted, 10 end
+    n_u = _hip.wino_plane_elems(wb_in.numel())
+    u_planes = torch.zeros(3 * n_u, device=dev, dtype=torch.int16)
+    table = torch.tensor([[0, 2 * H // 16, H]], dtype=torch.int64, device=dev)
+    call("glowtts_wino_weights", ptr(wb_in), wb_in.numel(), ptr(table), 1, ptr(u_planes), n_u)
+    _hip.conv_bind_wino(wb_in, u_planes)
+    _hip.set_knob("WINO_BWD", 1)
     rd = lib.glowtts_debug_trace_read_wino
 if which == "wrw5" and split and "wrw" in split and os.environ.get("GLOWTTS_WRW_TR", "1") != "0":
     rd = lib.glowtts_debug_trace_read_tr            # the frame-major / transposed-read kernel (convwrw_tr.hip)

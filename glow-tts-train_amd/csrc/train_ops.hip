@@ -209,6 +209,35 @@ __global__ __launch_bounds__(256) void clip_kernel(float *__restrict__ g, long n
     if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
 }
 
+// The same pass over a gradient that is the SUM of several micro-batches' gradients (train.train_batches): x = g * scale first
+// (scale = 1 / micro-batches, the mean an AVG all-reduce over as many ranks would leave), then the norm and the clamp of x — the
+// averaging costs no pass of its own over the flat buffer.  scale == 1 reproduces clip_kernel bit for bit.
+template <int V>
+__global__ __launch_bounds__(256) void clip_scaled_kernel(float *__restrict__ g, long nv, float scale, float clip,
+                                                          float *__restrict__ sumsq) {
+    __shared__ float red[4];
+    float s = 0.f;
+    const long stride = (long)gridDim.x * 256;
+    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < nv; i0 += 4 * stride) {
+        Vec<V> gv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            gv[u] = (i0 + u * stride < nv) ? Vec<V>::load(g + (i0 + u * stride) * V) : Vec<V>::zero();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const float x = gv[u][j] * scale;
+                s += x * x;
+                gv[u][j] = fminf(fmaxf(x, -clip), clip);
+            }
+            if (i0 + u * stride < nv) gv[u].store(g + (i0 + u * stride) * V);
+        }
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
+}
+
 __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model, float warmup) {
     if (warmup <= 0.f) return lr;
     // optimize.py:32-41 — lr * d^-0.5 * min(s^-0.5, s * w^-1.5); fp64 like the reference's numpy arithmetic
@@ -394,6 +423,18 @@ extern "C" int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *s
     else
         hipLaunchKernelGGL((clip_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, clip, sumsq);
     GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value");
+}
+
+extern "C" int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, float clip, float *sumsq, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(g, "glowtts_clip_grad_value_scaled: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value_scaled: bad argument");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((n & 3) == 0 && aligned16(g))
+        hipLaunchKernelGGL((clip_scaled_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, g, (long)(n / 4), scale, clip, sumsq);
+    else
+        hipLaunchKernelGGL((clip_scaled_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, scale, clip, sumsq);
+    GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value_scaled");
 }
 
 extern "C" int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state,

@@ -87,6 +87,7 @@ _SIGNATURES = {
     "glowtts_duration_loss_bwd": [_P, _P, _P, _P, _P, _L],
     "glowtts_span_logw": [_P, _P, _P, _I, _I],
     "glowtts_clip_grad_value": [_P, _L, _F, _P],
+    "glowtts_clip_grad_value_scaled": [_P, _L, _F, _F, _P],
     "glowtts_adam_noam": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F],
     "glowtts_adam_advance": [_P, _F, _F, _F],
     # whole WN stack per call (csrc/wn_stack.hip); the first argument is a HOST array of WnLayer
@@ -531,3 +532,21 @@ class zero_scope:
 
 def scratch_zeros(shape, device) -> torch.Tensor:
     return _arena.zeros(tuple(shape) if not isinstance(shape, int) else (shape,), device)
+
+
+class _WeightsState:
+    """State of `convops.weights_unchanged()` (gradient accumulation: the weights do not change between the micro-batches of
+    one update, so what is derived from them alone is made once per update).  It lives here because the operators of ops.py,
+    convops.py and the optimizer all read it.
+      active — inside the scope: a request for weight-derived data may be answered with what the same `epoch` already made;
+      epoch  — counts the times the weights may have changed (`convops.weights_changed()`); everything derived from the weights
+               remembers the epoch it was made in, and only data of the CURRENT epoch is ever reused;
+      record — loose results (a single convolution's packed weights, one flow's W^-1) are kept in `loose` for the scope to find;
+               off outside an accumulated update, so that nothing outlives the step that made it on the ordinary path."""
+
+    def __init__(self):
+        self.active, self.epoch, self.record = False, 0, False
+        self.loose: dict = {}
+
+
+weights_state = _WeightsState()

@@ -99,9 +99,60 @@ def _dense(x: torch.Tensor) -> torch.Tensor:
     return x if _rows_ok(x) else x.contiguous()
 
 
+# ---- weights packed once per update (gradient accumulation, train.train_batches) ------------------------------------------------
+# Everything a forward derives from the weights ALONE — weight norm + k-packing, the bf16 planes, the Winograd-domain planes, W^-1
+# and log det W of the invertible 1x1 convolutions — is the same for every micro-batch of one update.  `weights_changed()` opens a
+# new epoch (train_batches calls it before the first micro-batch, which then packs as every step does); inside
+# `weights_unchanged()` a request is skipped when the SAME epoch already served it from the same parameter storage in the same
+# arithmetic.  Anything else packs: a plan rebuilt because a parameter moved, a plan the update has not used yet, a mode flipped.
+_WS = _hip.weights_state
+
+
+def weights_changed(record: bool = False) -> None:
+    """The parameters may have been written since the last packing: nothing packed so far may be reused.  `record`: keep the loose
+    results (single convolutions, per-flow W^-1) of the forwards that follow for a `weights_unchanged()` scope to find."""
+    _WS.epoch += 1
+    _WS.record = bool(record)
+    _WS.loose.clear()
+
+
+class weights_unchanged:
+    """`with weights_unchanged():` — the caller guarantees that no parameter is written between the last `weights_changed()` and
+    the end of the block (train.train_batches: micro-batches 1.. of one update).  Never spans an optimizer step: FlatAdam.step
+    raises inside it.  Leaving the block ends the recording and drops the loose results."""
+
+    def __enter__(self):
+        if _WS.active:
+            raise RuntimeError("weights_unchanged() is not re-entrant")
+        _WS.active = True
+        return self
+
+    def __exit__(self, *exc):
+        _WS.active, _WS.record = False, False
+        _WS.loose.clear()
+        return False
+
+
+def _pack_state(version, tag=None):
+    """What a packing depends on besides the parameter values: the plan's build, the conv arithmetic (which planes ride along),
+    the Winograd switches (which Winograd-domain planes are made) and the caller's tag (the bf16-I/O mode of a flow block)."""
+    return (_WS.epoch, version, _MATH_NAME[0], bool(_WINO and _hip.get_knob("WINO")), bool(_hip.get_knob("WINO_BWD")), tag)
+
+
 def pack_weight(v: torch.Tensor, g: Optional[torch.Tensor], want_bwd: bool = True):
     """weight (Cout, Cin, taps) [+ weight-norm gain (Cout,1,1)] -> k-packed forward / backward-data layouts
     wp_f[tap][ceil(Cin/16)][Cout][16], wp_b[tap][ceil(Cout/16)][Cin][16] (taps flipped), and 1/||v|| per output channel."""
+    if _WS.active or _WS.record:
+        key = ("pack", v.data_ptr(), 0 if g is None else g.data_ptr(), tuple(v.shape), bool(want_bwd))
+        if _WS.active and key in _WS.loose:
+            return _WS.loose[key]
+        out = _pack_weight(v, g, want_bwd)
+        _WS.loose[key] = out
+        return out
+    return _pack_weight(v, g, want_bwd)
+
+
+def _pack_weight(v, g, want_bwd):
     v = f32(v.detach().contiguous())
     cout, cin, taps = v.shape
     dev = v.device
@@ -492,7 +543,16 @@ class WNPackPlan:
             self.wp_planes = torch.zeros(3 * self.wp_arena.numel(), device=self.wp_arena.device, dtype=torch.int16)
         return self.wp_arena, self.wp_planes
 
-    def pack(self):
+    def pack(self, tag=None):
+        if _WS.active or _WS.record:
+            # an accumulated update (weights_unchanged): the packed weights, planes and Winograd-domain planes this plan made
+            # earlier in the SAME epoch, build and arithmetic are those of these weights — nothing is launched, nothing goes stale
+            state = _pack_state(self.version, tag)
+            if _WS.active and getattr(self, "_packed", None) == state:
+                return
+            self._packed = state
+        else:
+            self._packed = None
         self.pack_count = getattr(self, "pack_count", 0) + 1      # (planes made from the packed weights go stale here)
         if _SPLIT_MATH[0] and self.want_planes:   # bf16-plane arithmetic is on: the planes of the new weights in the same pass
             arena, planes = self._plane_home(True)
@@ -590,9 +650,15 @@ class StackArena:
             self.planes = torch.zeros(3 * self.arena.numel(), device=self.arena.device, dtype=torch.int16)
         return self.planes
 
-    def pack(self, plans, conv_params, n_convs):
+    def pack(self, plans, conv_params, n_convs, tag=None):
         keys = tuple(WNPackPlan.make_key(cp) for cp in conv_params)
-        if keys != self.keys or any(p.shared is not self for p in plans):
+        rebuild = keys != self.keys or any(p.shared is not self for p in plans)
+        if _WS.active or _WS.record:
+            # (WNPackPlan.pack: the stack's one pack + Winograd launch is made once per accumulated update; a rebuild packs)
+            state = None if rebuild else _pack_state(tuple(p.version for p in plans), tag)
+            if _WS.active and state is not None and getattr(self, "_packed", None) == state:
+                return
+        if rebuild:
             sizes = [WNPackPlan.arena_floats(cp, n_convs) for cp in conv_params]
             if getattr(self, "arena", None) is not None and self.arena.is_cuda and not torch.cuda.is_current_stream_capturing():
                 # a REBUILD (a parameter moved: rare) drops the old packed buffer and planes, which kernels queued on the forward
@@ -610,8 +676,10 @@ class StackArena:
             self.desc = torch.cat([p.desc for p in plans]).contiguous()
             self.prefix = torch.tensor(rows, dtype=torch.int32).to(self.arena.device)
             self.n_conv, self.total_rows, self.keys = self.desc.shape[0], rows[-1], keys
+        self._packed = _pack_state(tuple(p.version for p in plans), tag) if (_WS.active or _WS.record) else None
         for p in plans:
             p.pack_count = getattr(p, "pack_count", 0) + 1
+            p._packed = None                          # (the plan's own record is of a packing into its slice by itself)
         if _SPLIT_MATH[0] and plans[0].want_planes:
             call("glowtts_pack_weight_planes_multi", ptr(self.desc), ptr(self.prefix), self.n_conv, self.total_rows, ptr(self.arena),
                  self.arena.numel(), ptr(self.planes_buffer(True)))
@@ -1191,7 +1259,7 @@ class FlowBlockFn(Function):
         dev = x.device
         plan = bplan.plan
         plan.ensure(FlowBlockPlan.conv_params(params, n_layers), n_convs=2 + 2 * n_layers)
-        plan.pack()
+        plan.pack(tag=io)
         bound = bplan.bind(io)
         try:
             new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)                      # noqa: E731
@@ -1204,6 +1272,14 @@ class FlowBlockFn(Function):
             xs = act(n_layers - 1, B, H, T) if n_layers > 1 else None
             logdet = new(B)
             winv = new(n_split * n_split + 1)
+            w_reuse = False                              # (an accumulated update: W^-1 / log det W of the update's first micro-batch)
+            if _WS.active or _WS.record:
+                wk = (_WS.epoch, n_split, params[2].data_ptr())
+                cached = getattr(bplan, "_winv_cache", None)
+                if _WS.active and cached is not None and cached[0] == wk:
+                    winv, w_reuse = cached[1], True
+                else:
+                    bplan._winv_cache = (wk, winv)
             if p_drop > 0.0 and (drop is None or tuple(drop.shape) != (n_layers, B, 2 * H, T) or not drop.is_contiguous()):
                 drop = ops.keep_mask((n_layers, B, 2 * H, T), p_drop, dev, f"decoder.block.{cfg[7] if len(cfg) > 7 else 0}")
             if p_drop <= 0.0:
@@ -1217,7 +1293,7 @@ class FlowBlockFn(Function):
                 cond_l = f32(cond.detach()).reshape(B, n_layers, 2 * H).permute(1, 0, 2).contiguous()
             call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(x_len), ptr(cond_l), ptr(drop), scale, ptr(y), ptr(y0h),
                  ptr(h0), ptr(xs), ptr(acts), ptr(ts), ptr(skip), ptr(out), ptr(z), ptr(logdet), B, C, H, T, taps, dil_rate, n_split,
-                 int(sigmoid_scale), int(io))
+                 int(sigmoid_scale), int(io) | (1024 if w_reuse else 0))
         finally:
             bplan.unbind(bound)
         ctx.save_for_backward(x, m2, x_len, y, h0, acts, ts, skip, out, winv, *([] if xs is None else [xs]),
@@ -1340,6 +1416,19 @@ class FlowStackFn(Function):
         pa, pts, pxs, pld, pw = ptr(acts), ptr(ts), ptr(xs), ptr(logdets), ptr(winv)
         pdr = ptr(drops)
         taps = params[8].shape[2]
+        # an accumulated update (weights_unchanged): W^-1 / log det W of every block as the update's first micro-batch made them
+        w_reuse = False
+        if _WS.active or _WS.record:
+            o2, wk = 0, [_WS.epoch, n_split]
+            for k in range(nb):
+                wk.append(params[o2 + 2].data_ptr())
+                o2 += counts[k]
+            cached = getattr(bplans[0], "_winv_cache", None)
+            if _WS.active and cached is not None and cached[0] == wk:
+                winv, w_reuse = cached[1], True
+                pw = ptr(winv)
+            else:
+                bplans[0]._winv_cache = (wk, winv)
         # fp32 tensors: block k's affine apply runs fused with block k + 1's ActNorm + InvConv (one pass over the flow tensor
         # instead of two; z_k is never written) — the block executors are told to leave those launches out (io bits 8 / 9)
         fuse = _FUSE_FLOWS and io == 0 and nb > 1 and n_split in (2, 4)      # (the fused kernels keep a group in registers: N <= 4)
@@ -1355,10 +1444,10 @@ class FlowStackFn(Function):
             for k in range(nb):
                 cps.append(FlowBlockPlan.conv_params(params[o2: o2 + counts[k]], n_layers))
                 o2 += counts[k]
-            st.pack([bp.plan for bp in bplans], cps, 2 + 2 * n_layers)
+            st.pack([bp.plan for bp in bplans], cps, 2 + 2 * n_layers, tag=io)
         # W^-1 and log det W of every block's invertible 1x1 convolution: one launch (a table of the weights' addresses, cached)
         stack_prep = _STACK_PACK and nb > 1
-        if stack_prep:
+        if stack_prep and not w_reuse:
             o2, wkey = 0, []
             for k in range(nb):
                 wkey.append(params[o2 + 2].data_ptr())
@@ -1391,14 +1480,14 @@ class FlowStackFn(Function):
             plan = bplan.plan
             if not stack_pack:
                 plan.ensure(FlowBlockPlan.conv_params(pk, n_layers), n_convs=2 + 2 * n_layers)
-                plan.pack()
+                plan.pack(tag=io)
             bound = bplan.bind(io)
             try:
                 tab = bplan.table(pk, n_layers)
                 tab.w_inv = pw + k * (n_split * n_split + 1) * 4
                 tab.logdet_w = tab.w_inv + 4 * n_split * n_split
                 tab.reserved = B if halves > 1 else 0    # utterances per layer slab when a call covers only a part of them
-                flags = int(io) | (1024 if stack_prep else 0)
+                flags = int(io) | (1024 if (stack_prep or w_reuse) else 0)
                 if halves > 1:
                     flags |= (256 | 4096 if k > 0 else 0) | (512 | 2048 if k < nb - 1 else 0)
                     sig_i = int(sigmoid_scale)
@@ -1420,7 +1509,7 @@ class FlowStackFn(Function):
                     tab.reserved = 0                 # (read by the calls above while they queued their launches; the table is cached)
                     prev_tab = tab
                     continue
-                if fuse and k > 0 and not stack_prep:
+                if fuse and k > 0 and not stack_prep and not w_reuse:
                     call("glowtts_invconv_prepare", ptr(pk[2]), tab.w_inv, tab.logdet_w, n_split)
                 if boundary and k > 0:
                     call("glowtts_flow_boundary_fwd", psk + (k - 1) * nH * 4, prev_tab.wf_end, prev_tab.b_end, py + (k - 1) * nC * 4, pm,

@@ -154,9 +154,15 @@ def invconv_prepare(weight: torch.Tensor):
     """(W^-1, log det W) of the n x n mixing matrix on one wavefront (replaces torch.inverse / torch.logdet)."""
     w = f32(_c(weight.detach()))
     n = w.shape[0]
+    ws = _hip.weights_state
+    key = ("winv", w.data_ptr(), n)
+    if ws.active and key in ws.loose:          # an accumulated update (convops.weights_unchanged): made by its first micro-batch
+        return ws.loose[key]
     w_inv = torch.empty_like(w)
     logdet_w = torch.empty(1, device=w.device, dtype=torch.float32)
     call("glowtts_invconv_prepare", ptr(w), ptr(w_inv), ptr(logdet_w), n)
+    if ws.active or ws.record:
+        ws.loose[key] = (w_inv, logdet_w)
     return w_inv, logdet_w
 
 

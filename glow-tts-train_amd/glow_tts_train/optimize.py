@@ -15,7 +15,7 @@ from operator import is_ as _is
 import numpy as np
 import torch
 
-from ._hip import call, ptr
+from ._hip import call, ptr, weights_state
 
 _ALIGN = 64  # elements: every parameter starts on a 256-byte boundary of the flat buffers
 
@@ -97,20 +97,26 @@ class FlatAdam(torch.optim.Optimizer):
         views = self._grad_views()
         return all(map(_is, [p.grad for p in self._params], views))        # (C-level loops: called twice per step)
 
-    def clip_grad_value_(self, clip_value: float):
+    def clip_grad_value_(self, clip_value: float, scale: float = 1.0):
         """utils.clip_grad_value_ over the whole flat gradient buffer in one launch; None if a gradient has been replaced by
-        a foreign tensor (the caller then takes the general path)."""
+        a foreign tensor (the caller then takes the general path).  `scale` != 1: the buffer holds a SUM of micro-batch
+        gradients (train.train_batches) and is multiplied by `scale` in the same pass, before the norm and the clamp."""
         if not self.grads_in_place():
             return None
         from .utils import _FlatGradView
         sumsq = torch.zeros(1, device=self.flat_g.device, dtype=torch.float32)
-        call("glowtts_clip_grad_value", ptr(self.flat_g), self.flat_g.numel(), float(clip_value), ptr(sumsq))
+        if scale != 1.0:
+            call("glowtts_clip_grad_value_scaled", ptr(self.flat_g), self.flat_g.numel(), float(scale), float(clip_value), ptr(sumsq))
+        else:
+            call("glowtts_clip_grad_value", ptr(self.flat_g), self.flat_g.numel(), float(clip_value), ptr(sumsq))
         return _FlatGradView(sumsq, 2.0)
 
     @torch.no_grad()
     def step(self, closure=None):
         if closure is not None:
             raise NotImplementedError("FlatAdam.step: closures are not supported")
+        if weights_state.active:                      # (convops.weights_unchanged: packed weights are being reused as they are)
+            raise RuntimeError("FlatAdam.step inside convops.weights_unchanged(): the scope must end before the weights change")
         if not self.grads_in_place():                 # a foreign hook may have replaced .grad: fold it back in
             views = self._grad_views()
             for i, (p, o) in enumerate(zip(self._params, self.offsets)):

@@ -101,6 +101,10 @@ class FlowBlockReducer:
         self._bucket_events: typing.List[typing.Tuple[int, bool, typing.Any, typing.Any, typing.Any]] = []
         self._in_finish = False
         self.launched_in_backward = 0          # buckets whose collective was issued before finish() in the last step
+        self.launched_last_update = 0          # collectives of the last update, finish()'s own included (one per bucket: under
+                                               # gradient accumulation N micro-batches share them, see no_sync)
+        self.collectives_launched = 0          # collectives issued by this reducer since it was built
+        self._no_sync = False
         if comm_thread is None:
             comm_thread = os.environ.get("GLOWTTS_DP_COMM_THREAD", "1") != "0"
         self._thread_mode = bool(comm_thread) and self._active and flat.flat_g.is_cuda
@@ -196,7 +200,29 @@ class FlowBlockReducer:
             except BaseException as exc:               # surfaced by finish() on the training thread
                 self._thr_error = exc
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """DistributedDataParallel.no_sync's meaning: backward passes inside the block only ACCUMULATE into the flat gradient
+        buffer — gradient announcements and hooks are ignored, no collective is launched, and `finish()` must not be called.  The
+        first backward after the block reduces the accumulated gradient (train.train_batches wraps every micro-batch of an update
+        but the last: one set of collectives per update, on the sum, with the usual overlap with that last backward)."""
+        if self._no_sync:
+            raise RuntimeError("FlowBlockReducer.no_sync() is not re-entrant")
+        if any(self._launched) or self._works:
+            raise RuntimeError("FlowBlockReducer.no_sync(): collectives of an unfinished step are in flight; call finish() first")
+        self._no_sync = True
+        try:
+            yield self
+        finally:
+            self._no_sync = False
+            # nothing was counted inside the block; whatever an earlier, abandoned backward left is dropped with it
+            self._announced.clear()
+            self._seen.clear()
+            self._pending = [b.n_params for b in self.buckets]
+            self._launched = [False] * len(self.buckets)
+
     def _launch(self, i: int):
+        self.collectives_launched += 1
         b = self.buckets[i]
         view = self.flat.flat_g[b.lo:b.hi]
         if self._thread_mode:
@@ -263,12 +289,14 @@ class FlowBlockReducer:
         # AccumulateGrad hooks also fire for parameters whose gradient an operator writes in place (it hands autograd None),
         # and they fire when that operator's backward RETURNS — before a deferred un-packing on another stream has run.
         # For those parameters (convops._mark_direct) only the operator's own announcement counts.
-        if getattr(p, "_glowtts_direct", False):
+        if self._no_sync or getattr(p, "_glowtts_direct", False):
             return
         self._on_grad(p)
 
     def _on_announce(self, params):
         """convops._notify: the gradients of `params` (a list) are complete on the current stream."""
+        if self._no_sync:
+            return
         bucket_of, seen, pending = self._bucket_of, self._seen, self._pending
         ready = []
         for p in params:
@@ -285,7 +313,7 @@ class FlowBlockReducer:
             self._launch(i)
 
     def _on_grad(self, p: torch.Tensor):
-        if id(p) not in self._bucket_of or id(p) in self._seen:
+        if self._no_sync or id(p) not in self._bucket_of or id(p) in self._seen:
             return
         self._seen.add(id(p))
         i = self._bucket_of[id(p)]
@@ -296,6 +324,10 @@ class FlowBlockReducer:
     def finish(self):
         """Call after backward(), before clipping: reduces buckets whose parameters got no gradient this step (their
         slice is the zeros left by zero_grad), then makes the current stream wait for every collective."""
+        if self._no_sync:
+            raise RuntimeError("FlowBlockReducer.finish() inside no_sync(): the gradients of this backward are not reduced; "
+                               "run the update's last backward outside the block and finish() after it")
+        before = self.collectives_launched - sum(self._launched)
         if self._active:
             self.launched_in_backward = sum(self._launched)
             self._in_finish = True
@@ -329,6 +361,7 @@ class FlowBlockReducer:
                 h = self._hook_of.pop(pid, None)
                 if h is not None:
                     h.remove()
+        self.launched_last_update = self.collectives_launched - before
         self._announced.clear()
         self._works.clear()
         self._seen.clear()

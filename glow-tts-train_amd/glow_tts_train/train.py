@@ -5,6 +5,10 @@ The reference pays >= 521 device->host syncs per step (two `loss.item()` plus on
 the alignment search never leaves the GPU, and (with `reducer`) gradient all-reduce overlaps the backward.
 `train()` is the reference's epoch loop around it (checkpoint cadence included); batches reach HBM one step ahead
 through `dataset.DeviceBatches`.
+
+Gradient accumulation (`train_batches`, `accum_steps=`): one update from N micro-batches, each normalised by its own frames and
+tokens, the gradients summed in the flat buffer and averaged inside the clip kernel — what N data-parallel ranks with an AVG
+all-reduce compute (DistributedDataParallel, reference __main__.py:268-271) on one GPU; the weights are packed once per update.
 """
 from __future__ import annotations
 
@@ -15,7 +19,10 @@ from pathlib import Path
 
 import torch
 
-from ._hip import join_side_streams, zero_scope
+import contextlib
+
+from . import convops
+from ._hip import call, join_side_streams, ptr, zero_scope
 from .convops import flush_groups
 from .utils import clip_grad_value_, duration_loss, mle_loss
 
@@ -23,10 +30,10 @@ _LOGGER = logging.getLogger("glow_tts_train")
 
 
 def train(train_loader, config, model_dir: Path, model=None, optimizer=None, global_step: int = 1,
-          checkpoint_epochs: int = 1, rank: int = 0, reducer=None):
+          checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1):
     """Epoch loop of the reference (train.py:19-88): seed, build or adopt model and optimizer, run `config.epochs`
     passes over `train_loader`, and on rank 0 write `checkpoint_<step>.pth` + `config_<step>.json` into `model_dir`
-    every `checkpoint_epochs` epochs.  Returns the final global step."""
+    every `checkpoint_epochs` epochs.  Returns the final global step.  `accum_steps`: loader batches per update (train_step)."""
     from .checkpoint import Checkpoint, save_checkpoint
     from .models import setup_model
 
@@ -37,7 +44,7 @@ def train(train_loader, config, model_dir: Path, model=None, optimizer=None, glo
     for epoch in range(1, config.epochs + 1):
         started = time.perf_counter()
         global_step = train_step(global_step=global_step, epoch=epoch, model=model, optimizer=optimizer, config=config,
-                                 train_loader=train_loader, fp16_run=config.fp16_run, reducer=reducer,
+                                 train_loader=train_loader, fp16_run=config.fp16_run, reducer=reducer, accum_steps=accum_steps,
                                  on_loss=lambda e, loss, step: _LOGGER.info(
                                      "Avg. Loss for epoch %s: %s (global step=%s)", e, loss, step))
         if epoch % checkpoint_epochs == 0 and rank == 0:
@@ -93,6 +100,78 @@ def train_batch(model, optimizer, batch, grad_clip: float, reducer=None, scaler=
     return loss
 
 
+def _accumulate(model, optimizer, batches, reducer=None, reuse_packs: bool = True):
+    """The accumulating part of `train_batches`: zero the gradients once, then forward + loss + backward of every micro-batch,
+    each adding into the flat gradient buffer (every operator accumulates into `.grad`: include/glowtts_hip.h, conventions).
+    Returns the micro-batches' (device) losses.  No clipping, no update."""
+    batches = list(batches)
+    if not batches:
+        raise ValueError("train_batches: no micro-batch given")
+    m = len(batches)
+    optimizer.zero_grad()
+    if m > 1:
+        convops.weights_changed(record=reuse_packs)      # micro-batch 0 packs as every step does; the rest of the update reuses it
+    losses = []
+    with contextlib.ExitStack() as scope:
+        for k, (x, x_lengths, y, y_lengths, speaker_ids) in enumerate(batches):
+            last = k == m - 1
+            if k == 1 and reuse_packs:
+                scope.enter_context(convops.weights_unchanged())
+            # all but the last backward only accumulate; the last one announces the gradients as a plain step does, so the
+            # overlapped all-reduce runs once, on the sum
+            defer = reducer.no_sync() if (reducer is not None and not last) else contextlib.nullcontext()
+            with defer, zero_scope(y.device):
+                (z, z_m, z_logs, logdet, z_mask), _, (_attn, logw, logw_) = model(x, x_lengths, y, y_lengths, g=speaker_ids)
+                loss = mle_loss(z, z_m, z_logs, logdet, z_mask) + duration_loss(logw, logw_, x_lengths)
+                loss.backward()
+                join_side_streams()
+                flush_groups()
+                if reducer is not None and last:
+                    reducer.finish()
+                losses.append(loss.detach())
+    return losses
+
+
+def _scale_clip_per_tensor(parameters, scale: float, clip_value: float) -> None:
+    """The general path of utils.clip_grad_value_ (a gradient replaced by a foreign tensor) for an accumulated gradient."""
+    sumsq = None
+    for p in parameters:
+        if p.grad is None:
+            continue
+        g = p.grad.data
+        if not g.is_contiguous():
+            g = g.contiguous()
+            p.grad.data = g
+        if sumsq is None:
+            sumsq = torch.zeros(1, device=g.device, dtype=torch.float32)
+        call("glowtts_clip_grad_value_scaled", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq))
+
+
+def train_batches(model, optimizer, batches, grad_clip: float, reducer=None, *, reuse_packs: bool = True) -> torch.Tensor:
+    """ONE optimisation step from a non-empty sequence of already-resident micro-batches (they may differ in B, T_text and
+    T_mel); returns the mean of their losses as a device tensor, un-synchronised.
+
+    Every micro-batch's loss is normalised by its own frames and tokens exactly as `train_batch` does and is NOT scaled; the
+    gradients add up in the flat buffer and are multiplied by 1 / m inside the clip kernel (glowtts_clip_grad_value_scaled), then
+    clamped, then one Adam/Noam update: the arithmetic of m data-parallel ranks whose gradients an AVG all-reduce has averaged.
+    The step counters advance once.  One micro-batch issues the launches of `train_batch`.
+
+    What depends on the weights alone (weight norm + packing, bf16 and Winograd planes, W^-1 / log det W) is made by the first
+    micro-batch and reused by the others (`convops.weights_unchanged`; `reuse_packs=False` makes every micro-batch redo it).
+    With `reducer`, all micro-batches but the last run under `reducer.no_sync()`."""
+    losses = _accumulate(model, optimizer, batches, reducer, reuse_packs)
+    m = len(losses)
+    flat = getattr(optimizer, "_optim", optimizer)
+    scale = 1.0 / m
+    if not (hasattr(flat, "clip_grad_value_") and flat.clip_grad_value_(grad_clip, scale=scale) is not None):
+        if m == 1:
+            clip_grad_value_(model.parameters(), grad_clip)
+        else:
+            _scale_clip_per_tensor(model.parameters(), scale, grad_clip)
+    optimizer.step()
+    return losses[0] if m == 1 else torch.stack(losses).mean()
+
+
 class GraphedTrainStep:
     """The whole training step (zero_grad .. Adam/Noam) captured once into a hipGraph and replayed per batch.
 
@@ -128,15 +207,26 @@ class GraphedTrainStep:
 
 
 def train_step(global_step: int, epoch: int, model, optimizer, config, train_loader, fp16_run: bool = False,
-               scaler=None, reducer=None, on_loss: typing.Optional[typing.Callable] = None) -> int:
+               scaler=None, reducer=None, on_loss: typing.Optional[typing.Callable] = None, accum_steps: int = 1) -> int:
     """Same signature and return value as the reference's `train_step` (train.py:91-100).
 
     `fp16_run` (reference train.py:116-121, 133-141: `autocast()` + GradScaler) selects the reduced-precision form of THIS
     build: the flow decoder keeps its activation tensors in HBM as bf16 (`decoder.io_bf16 = "all"`, models.FlowSpecDecoder)
     with fp32 parameters, log-determinants and accumulation, and the text encoder's attention contractions run on the bf16
     matrix pipe (`MultiHeadAttention.bf16_mma`).  bf16 has fp32's exponent range, so no loss scaling is needed:
-    `scaler` may be None; a GradScaler that is passed in is driven exactly as the reference drives it."""
+    `scaler` may be None; a GradScaler that is passed in is driven exactly as the reference drives it.
+
+    `accum_steps` (not part of the reference signature): loader batches per update.  N > 1 groups the batches N at a time into one
+    `train_batches` update (a tail of m < N batches at the end of the epoch makes one update averaged over m); `global_step`
+    counts updates, `on_loss` receives the mean over updates.  Not combined with a GradScaler."""
     from .dataset import DeviceBatches
+
+    accum_steps = int(accum_steps)
+    if accum_steps < 1:
+        raise ValueError(f"train_step: accum_steps must be >= 1, got {accum_steps}")
+    if accum_steps > 1 and scaler is not None:
+        raise ValueError("train_step: accum_steps > 1 together with a GradScaler (scaler=...) is not supported; "
+                         "fp16_run without a scaler (bf16 tensors need no loss scaling) is")
 
     model.train()
     bare = model.module if hasattr(model, "module") else model
@@ -152,8 +242,19 @@ def train_step(global_step: int, epoch: int, model, optimizer, config, train_loa
     losses = []
     device = next(model.parameters()).device
     try:
+        group = []
         for batch in DeviceBatches(train_loader, device):      # batch k+1 is copied to HBM while step k runs
-            losses.append(train_batch(model, optimizer, batch, config.grad_clip, reducer, scaler if fp16_run else None))
+            if accum_steps == 1:
+                losses.append(train_batch(model, optimizer, batch, config.grad_clip, reducer, scaler if fp16_run else None))
+                global_step += 1
+                continue
+            group.append(batch)
+            if len(group) == accum_steps:
+                losses.append(train_batches(model, optimizer, group, config.grad_clip, reducer))
+                global_step += 1
+                group = []
+        if group:                                               # the epoch's tail: one update averaged over what is left
+            losses.append(train_batches(model, optimizer, group, config.grad_clip, reducer))
             global_step += 1
     finally:
         if decoder is not None:

@@ -754,11 +754,16 @@ int glowtts_span_logw(const int32_t *first, const int32_t *t_x, float *logw_, in
 
 /* ---- clip_grad_value_ (utils.py:118-132) and Adam + Noam (optimize.py:8-64) over FLAT buffers ---------------
  * clip : sumsq[0] += sum g^2 (pre-clamp, as the reference's norm) ; g = clamp(g, -clip, clip)
+ * clip_scaled : the same pass over a gradient SUMMED over several micro-batches (gradient accumulation): x = g * scale,
+ *        sumsq[0] += sum x^2 (pre-clamp), g = clamp(x, -clip, clip) — utils.py:118-132 applied to the mean gradient that
+ *        DistributedDataParallel's all-reduce leaves on every rank (__main__.py:268-271), scale = 1 / contributions;
+ *        scale == 1 gives glowtts_clip_grad_value's result bit for bit
  * adam : state[0] = Adam step t (float, >= 1 at the call), state[1] = Noam step_num; the learning rate
  *        lr * dim_model^-0.5 * min(s^-0.5, s * warmup^-1.5) (or `lr` if warmup <= 0) is computed ON DEVICE from
  *        state so a captured graph replays with the right rate; torch.optim.Adam arithmetic (no amsgrad/decay).
  * adam_advance: state[0] += 1; state[1] += 1; state[2] = learning rate of the NEXT update (optimize.py:43-48) */
 int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *sumsq, glowtts_stream_t stream);
+int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state, float lr,
                       float beta1, float beta2, float eps, float dim_model, float warmup,
                       glowtts_stream_t stream);

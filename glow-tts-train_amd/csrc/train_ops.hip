@@ -4,6 +4,8 @@
 //   clip_grad_value_ over a flat buffer    (utils.py:118-132)   — replaces one .item() host sync PER PARAMETER TENSOR
 //   Adam + Noam schedule over flat buffers (optimize.py:8-64)   — learning rate derived on device from a step
 //                                                                  counter, so the whole step is hipGraph-capturable
+//   the same clip / Adam / Noam tail behind a device flag          (train.py:133-141: GradScaler.step's skip) — an update whose
+//                                                                  gradient holds a NaN or an Inf is skipped without a host read
 #include "common.hpp"
 
 namespace glowtts {
@@ -238,6 +240,42 @@ __global__ __launch_bounds__(256) void clip_scaled_kernel(float *__restrict__ g,
     if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
 }
 
+// clip_scaled_kernel that also tells whether the gradient may be applied at all (guard[0], include/glowtts_hip.h): fmaxf(NaN, -clip)
+// is -clip and an Inf clamps to +-clip, so after this pass a poisoned gradient looks like any other.  The test is on the exponent
+// bits of every x = g * scale, not on sumsq: the sum depends on the order of the atomics and can overflow over finite elements,
+// and data-parallel ranks holding the same reduced gradient must reach the same decision.  A workgroup that saw a non-finite x
+// stores 1 (every writer stores the same value: no atomic); a clean pass leaves guard[0] as it found it, so several launches
+// (one per gradient tensor) accumulate into one flag.  On a clean gradient g and sumsq are clip_scaled_kernel's, bit for bit.
+template <int V>
+__global__ __launch_bounds__(256) void clip_guarded_kernel(float *__restrict__ g, long nv, float scale, float clip,
+                                                           float *__restrict__ sumsq, float *__restrict__ guard) {
+    __shared__ float red[4];
+    float s = 0.f;
+    int bad = 0;
+    const long stride = (long)gridDim.x * 256;
+    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < nv; i0 += 4 * stride) {
+        Vec<V> gv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+            gv[u] = (i0 + u * stride < nv) ? Vec<V>::load(g + (i0 + u * stride) * V) : Vec<V>::zero();
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const float x = gv[u][j] * scale;
+                bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;     // exponent all ones: Inf or NaN
+                s += x * x;
+                gv[u][j] = fminf(fmaxf(x, -clip), clip);
+            }
+            if (i0 + u * stride < nv) gv[u].store(g + (i0 + u * stride) * V);
+        }
+    }
+    s = block_sum_256(s, red);
+    if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
+    const int any_bad = __syncthreads_or(bad);
+    if (threadIdx.x == 0 && any_bad) guard[0] = 1.0f;
+}
+
 __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model, float warmup) {
     if (warmup <= 0.f) return lr;
     // optimize.py:32-41 — lr * d^-0.5 * min(s^-0.5, s * w^-1.5); fp64 like the reference's numpy arithmetic
@@ -248,9 +286,9 @@ __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model
 }
 
 template <int V>
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, long nv, const float *__restrict__ state, float lr,
-                                                   float b1, float b2, float eps, float dim_model, float warmup) {
+__device__ __forceinline__ void adam_update(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                            float *__restrict__ v, long nv, const float *__restrict__ state, float lr, float b1,
+                                            float b2, float eps, float dim_model, float warmup) {
     // torch.optim.Adam (no amsgrad, no weight decay): step_size = lr_t / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
     const float t = state[0];
     // state[3] > 0: a learning rate imposed for this one update (a resumed optimizer applies the rate stored in its
@@ -278,12 +316,50 @@ __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const 
     }
 }
 
+template <int V>
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, long nv, const float *__restrict__ state, float lr,
+                                                   float b1, float b2, float eps, float dim_model, float warmup) {
+    adam_update<V>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup);
+}
+
+// The same update behind the flag the guarded clip pass left (guard[0] != 0: a non-finite gradient element was seen): the whole
+// grid leaves before it has read or written anything of p, m or v.
+template <int V>
+__global__ __launch_bounds__(256) void adam_guarded_kernel(float *__restrict__ p, const float *__restrict__ g,
+                                                           float *__restrict__ m, float *__restrict__ v, long nv,
+                                                           const float *__restrict__ state, const float *__restrict__ guard,
+                                                           float lr, float b1, float b2, float eps, float dim_model,
+                                                           float warmup) {
+    if (guard[0] != 0.f) return;
+    adam_update<V>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup);
+}
+
 __global__ void adam_advance_kernel(float *state, float lr, float dim_model, float warmup) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         state[0] += 1.0f;
         state[1] += 1.0f;
         state[2] = noam_rate(state[1], lr, dim_model, warmup);
         state[3] = 0.f;
+    }
+}
+
+// guard = [bad flag of the pending update, updates skipped, skipped consecutively up to now, updates applied].  A skipped update
+// leaves all of state alone — Adam's t, the Noam step, the next rate and a pending imposed rate (state[3]) stand still.
+__global__ void adam_advance_guarded_kernel(float *state, float *guard, float lr, float dim_model, float warmup) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        if (guard[0] == 0.f) {
+            state[0] += 1.0f;
+            state[1] += 1.0f;
+            state[2] = noam_rate(state[1], lr, dim_model, warmup);
+            state[3] = 0.f;
+            guard[3] += 1.0f;
+            guard[2] = 0.f;
+        } else {
+            guard[1] += 1.0f;
+            guard[2] += 1.0f;
+        }
+        guard[0] = 0.f;
     }
 }
 
@@ -455,6 +531,40 @@ extern "C" int glowtts_adam_advance(float *state, float lr, float dim_model, flo
     GLOWTTS_CHECK_ARG(state, "glowtts_adam_advance: null pointer");
     hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr, dim_model, warmup);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance");
+}
+
+extern "C" int glowtts_clip_grad_value_guarded(float *g, int64_t n, float scale, float clip, float *sumsq, float *guard,
+                                               glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(g && guard, "glowtts_clip_grad_value_guarded: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value_guarded: bad argument");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((n & 3) == 0 && aligned16(g))
+        hipLaunchKernelGGL((clip_guarded_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, g, (long)(n / 4), scale, clip, sumsq, guard);
+    else
+        hipLaunchKernelGGL((clip_guarded_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, scale, clip, sumsq, guard);
+    GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value_guarded");
+}
+
+extern "C" int glowtts_adam_noam_guarded(float *p, const float *g, float *m, float *v, int64_t n, const float *state,
+                                         const float *guard, float lr, float beta1, float beta2, float eps, float dim_model,
+                                         float warmup, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(p && g && m && v && state && guard, "glowtts_adam_noam_guarded: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam_guarded: negative size");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((n & 3) == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v))
+        hipLaunchKernelGGL((adam_guarded_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, p, g, m, v, (long)(n / 4), state, guard, lr, beta1, beta2, eps, dim_model, warmup);
+    else
+        hipLaunchKernelGGL((adam_guarded_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, (long)n, state, guard, lr, beta1, beta2, eps, dim_model, warmup);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_guarded");
+}
+
+extern "C" int glowtts_adam_advance_guarded(float *state, float *guard, float lr, float dim_model, float warmup,
+                                            glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(state && guard, "glowtts_adam_advance_guarded: null pointer");
+    hipLaunchKernelGGL(adam_advance_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, guard, lr, dim_model, warmup);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance_guarded");
 }
 
 // ------------------------------------------------------------------------------------------------------------

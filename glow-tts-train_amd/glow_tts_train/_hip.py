@@ -90,6 +90,10 @@ _SIGNATURES = {
     "glowtts_clip_grad_value_scaled": [_P, _L, _F, _F, _P],
     "glowtts_adam_noam": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F],
     "glowtts_adam_advance": [_P, _F, _F, _F],
+    # the same three behind the device-side "skip a non-finite update" flag (guard: float[4], include/glowtts_hip.h)
+    "glowtts_clip_grad_value_guarded": [_P, _L, _F, _F, _P, _P],
+    "glowtts_adam_noam_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F],
+    "glowtts_adam_advance_guarded": [_P, _P, _F, _F, _F],
     # whole WN stack per call (csrc/wn_stack.hip); the first argument is a HOST array of WnLayer
     "glowtts_wn_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I],
     "glowtts_wn_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -21,10 +21,18 @@ _ALIGN = 64  # elements: every parameter starts on a 256-byte boundary of the fl
 
 
 class FlatAdam(torch.optim.Optimizer):
-    """torch.optim.Adam arithmetic (no amsgrad / weight decay) over flat buffers, launched through the C ABI."""
+    """torch.optim.Adam arithmetic (no amsgrad / weight decay) over flat buffers, launched through the C ABI.
+
+    `skip_nonfinite` (off by default): an update whose gradient holds a NaN or an Inf is skipped on the device, with no host
+    read, so the step stays asynchronous and graph-capturable — the skip GradScaler.step gives the reference's fp16 runs
+    (train.py:133-141).  `guard` is then a 4-float device tensor [bad flag of the pending update, updates skipped, skipped
+    consecutively, updates applied].  The flag is PRODUCED by the clip pass (`clip_grad_value_` here, `utils.clip_grad_value_`,
+    both of `train`'s routes): `step()` skips exactly when a clip since the last step saw a non-finite element, so a caller
+    who does not clip gets an unguarded update, as without the option.  The counters are not part of `state_dict()` (the file
+    format is the reference's): they restart at zero on resume."""
 
     def __init__(self, params, lr=1.0, betas=(0.9, 0.98), eps=1e-9, dim_model: float = 0.0, warmup_steps: float = 0.0,
-                 base_lr: typing.Optional[float] = None):
+                 base_lr: typing.Optional[float] = None, skip_nonfinite: bool = False):
         params = [p for p in params]
         # the group carries every key torch.optim.Adam's does (amsgrad, weight_decay, foreach, ... at their defaults), so
         # state_dict() has torch's layout for this torch version and the reference loads it unchanged
@@ -32,7 +40,10 @@ class FlatAdam(torch.optim.Optimizer):
         super().__init__(params, {k: v for k, v in template.items() if k != "params"})
         self.base_lr = float(lr if base_lr is None else base_lr)
         self.dim_model, self.warmup = float(dim_model), float(warmup_steps)
+        self.guard: typing.Optional[torch.Tensor] = None
         self._build_flat()
+        if skip_nonfinite:
+            self.enable_skip_nonfinite()
 
     # -- layout -------------------------------------------------------------------------------------------------
     def _build_flat(self):
@@ -70,6 +81,12 @@ class FlatAdam(torch.optim.Optimizer):
         # zero_grad() has not run yet: the views just installed are the ones grads_in_place() compares against
         self._views = [p.grad for p in ps]
 
+    def enable_skip_nonfinite(self) -> None:
+        """Switch `skip_nonfinite` on for an optimizer built without it (train.train does, for the optimizer it built itself):
+        allocates `guard`; from the next clip pass on, the guarded kernels run."""
+        if self.guard is None:
+            self.guard = torch.zeros(4, device=self.flat_p.device, dtype=torch.float32)
+
     def slices(self):
         """(offset, numel) of every parameter inside the flat buffers, in construction order."""
         return [(o, p.numel()) for p, o in zip(self._params, self.offsets)]
@@ -100,12 +117,16 @@ class FlatAdam(torch.optim.Optimizer):
     def clip_grad_value_(self, clip_value: float, scale: float = 1.0):
         """utils.clip_grad_value_ over the whole flat gradient buffer in one launch; None if a gradient has been replaced by
         a foreign tensor (the caller then takes the general path).  `scale` != 1: the buffer holds a SUM of micro-batch
-        gradients (train.train_batches) and is multiplied by `scale` in the same pass, before the norm and the clamp."""
+        gradients (train.train_batches) and is multiplied by `scale` in the same pass, before the norm and the clamp.
+        With `skip_nonfinite` the pass also sets guard[0] when an element of the scaled gradient is not finite."""
         if not self.grads_in_place():
             return None
         from .utils import _FlatGradView
         sumsq = torch.zeros(1, device=self.flat_g.device, dtype=torch.float32)
-        if scale != 1.0:
+        if self.guard is not None:
+            call("glowtts_clip_grad_value_guarded", ptr(self.flat_g), self.flat_g.numel(), float(scale), float(clip_value),
+                 ptr(sumsq), ptr(self.guard))
+        elif scale != 1.0:
             call("glowtts_clip_grad_value_scaled", ptr(self.flat_g), self.flat_g.numel(), float(scale), float(clip_value), ptr(sumsq))
         else:
             call("glowtts_clip_grad_value", ptr(self.flat_g), self.flat_g.numel(), float(clip_value), ptr(sumsq))
@@ -127,13 +148,20 @@ class FlatAdam(torch.optim.Optimizer):
                     p.grad = views[i]
         g = self.param_groups[0]
         b1, b2 = g["betas"]
+        if self.guard is not None:
+            call("glowtts_adam_noam_guarded", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
+                 self.numel_padded, ptr(self.dev_state), ptr(self.guard), self.base_lr, float(b1), float(b2), float(g["eps"]),
+                 self.dim_model, self.warmup)
+            call("glowtts_adam_advance_guarded", ptr(self.dev_state), ptr(self.guard), self.base_lr, self.dim_model, self.warmup)
+            return
         call("glowtts_adam_noam", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
              self.numel_padded, ptr(self.dev_state), self.base_lr, float(b1), float(b2), float(g["eps"]),
              self.dim_model, self.warmup)
         call("glowtts_adam_advance", ptr(self.dev_state), self.base_lr, self.dim_model, self.warmup)
 
     def state_dict(self):
-        """torch.optim.Adam-compatible layout: state[i] = {step, exp_avg, exp_avg_sq} (what checkpoint.py:44 saves)."""
+        """torch.optim.Adam-compatible layout: state[i] = {step, exp_avg, exp_avg_sq} (what checkpoint.py:44 saves).  The
+        `skip_nonfinite` counters (`guard`) are not saved."""
         t = (self.dev_state[0] - 1.0).detach().cpu()        # ONE device read for the step every entry shares
         state = {}
         for i, (p, o) in enumerate(zip(self._params, self.offsets)):
@@ -209,7 +237,7 @@ class Adam:
     `.step() .zero_grad() .get_lr() .state_dict() .load_state_dict() .cur_lr .step_num ._optim`."""
 
     def __init__(self, params, scheduler, dim_model, warmup_steps: int = 4000, lr: float = 1e0,
-                 betas: typing.Tuple[float, float] = (0.9, 0.98), eps: float = 1e-9):
+                 betas: typing.Tuple[float, float] = (0.9, 0.98), eps: float = 1e-9, *, skip_nonfinite: bool = False):
         self.params = list(params)
         self.scheduler, self.dim_model, self.warmup_steps = scheduler, dim_model, warmup_steps
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -217,7 +245,8 @@ class Adam:
         self.cur_lr = lr * self._get_lr_scale()
         noam = scheduler == "noam"
         self._optim = FlatAdam(self.params, lr=self.cur_lr, betas=betas, eps=eps, base_lr=lr,
-                               dim_model=dim_model if noam else 0.0, warmup_steps=warmup_steps if noam else 0.0)
+                               dim_model=dim_model if noam else 0.0, warmup_steps=warmup_steps if noam else 0.0,
+                               skip_nonfinite=skip_nonfinite)
 
     def _get_lr_scale(self):
         if self.scheduler == "noam":
@@ -243,7 +272,30 @@ class Adam:
     def zero_grad(self):
         self._optim.zero_grad()
 
+    def sync_from_device(self) -> typing.Dict[str, int]:
+        """ONE device-to-host copy of the device's step state and the `skip_nonfinite` counters; sets `step_num`, `cur_lr` and
+        `param_groups[...]["lr"]` to the device's values and returns {"applied", "skipped", "consecutive_skipped"} (updates since
+        construction; they are not saved in checkpoints and restart at zero on resume).
+
+        `step()` (and GraphedTrainStep) advance the host mirror with every update ATTEMPT without asking the device; an update
+        the device skipped leaves the mirror one step ahead, and this call is the reconciliation.  Without `skip_nonfinite`
+        the skip counts are zero and the mirror already agrees: a no-op on a healthy run."""
+        flat = self._optim
+        if flat.guard is None:
+            host = flat.dev_state.detach().cpu().tolist() + [0.0] * 4
+        else:
+            host = torch.cat([flat.dev_state.detach(), flat.guard.detach()]).cpu().tolist()
+        if int(host[1]) != self.step_num:            # the mirror ran ahead: the schedule is re-derived from the device's step
+            self.step_num = int(host[1])
+            if self.scheduler == "noam":
+                self.cur_lr = self.lr * self._get_lr_scale()
+                for group in flat.param_groups:
+                    # a rate a resumed checkpoint imposed on the next update (dev_state[3]) is still pending after a skip
+                    group["lr"] = host[3] if host[3] > 0.0 else self.cur_lr
+        return {"applied": int(host[7]), "skipped": int(host[5]), "consecutive_skipped": int(host[6])}
+
     def load_state_dict(self, d):
+        """The `skip_nonfinite` counters are not part of the file: they keep their values (zero after construction)."""
         self._optim.load_state_dict(d)
 
     def state_dict(self):

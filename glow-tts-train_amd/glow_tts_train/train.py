@@ -9,6 +9,10 @@ through `dataset.DeviceBatches`.
 Gradient accumulation (`train_batches`, `accum_steps=`): one update from N micro-batches, each normalised by its own frames and
 tokens, the gradients summed in the flat buffer and averaged inside the clip kernel — what N data-parallel ranks with an AVG
 all-reduce compute (DistributedDataParallel, reference __main__.py:268-271) on one GPU; the weights are packed once per update.
+
+Non-finite updates (`skip_nonfinite=`, an optimizer built with `optimize.Adam(..., skip_nonfinite=True)`): the clip pass flags a
+gradient that holds a NaN or an Inf and the Adam/Noam kernels skip that update on the device — no host read on the step path;
+the epoch's one synchronisation also reads the skip counters (`Adam.sync_from_device`).
 """
 from __future__ import annotations
 
@@ -30,25 +34,32 @@ _LOGGER = logging.getLogger("glow_tts_train")
 
 
 def train(train_loader, config, model_dir: Path, model=None, optimizer=None, global_step: int = 1,
-          checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1):
+          checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1, skip_nonfinite: bool = False):
     """Epoch loop of the reference (train.py:19-88): seed, build or adopt model and optimizer, run `config.epochs`
     passes over `train_loader`, and on rank 0 write `checkpoint_<step>.pth` + `config_<step>.json` into `model_dir`
-    every `checkpoint_epochs` epochs.  Returns the final global step.  `accum_steps`: loader batches per update (train_step)."""
+    every `checkpoint_epochs` epochs.  Returns the final global step.  `accum_steps`: loader batches per update (train_step).
+    `skip_nonfinite`: skip updates whose gradient is not finite (train_step); an optimizer built here gets the option switched
+    on, one passed in must have been built with it."""
     from .checkpoint import Checkpoint, save_checkpoint
     from .models import setup_model
 
     torch.manual_seed(config.seed)
+    built_here = optimizer is None
     model, optimizer = setup_model(config, model=model, optimizer=optimizer)
     assert model is not None and optimizer is not None
+    if skip_nonfinite and built_here:
+        optimizer._optim.enable_skip_nonfinite()
     model_dir = Path(model_dir)
     for epoch in range(1, config.epochs + 1):
         started = time.perf_counter()
         global_step = train_step(global_step=global_step, epoch=epoch, model=model, optimizer=optimizer, config=config,
                                  train_loader=train_loader, fp16_run=config.fp16_run, reducer=reducer, accum_steps=accum_steps,
+                                 skip_nonfinite=skip_nonfinite,
                                  on_loss=lambda e, loss, step: _LOGGER.info(
                                      "Avg. Loss for epoch %s: %s (global step=%s)", e, loss, step))
         if epoch % checkpoint_epochs == 0 and rank == 0:
             path = model_dir / f"checkpoint_{global_step}.pth"
+            optimizer.sync_from_device()                    # the saved learning_rate is the device's, skipped updates or not
             save_checkpoint(Checkpoint(model=model, optimizer=optimizer, learning_rate=optimizer.cur_lr,
                                        global_step=global_step, version=config.version), path)
             with open(model_dir / f"config_{global_step}.json", "w") as config_file:
@@ -62,10 +73,15 @@ def train(train_loader, config, model_dir: Path, model=None, optimizer=None, glo
 def train_batch(model, optimizer, batch, grad_clip: float, reducer=None, scaler=None) -> torch.Tensor:
     """One optimisation step on one already-resident batch; returns the (device) loss tensor, un-synchronised.
     `scaler` (a torch GradScaler, reduced-precision runs only): the reference's sequence train.py:133-141 — scale the loss,
-    un-scale the gradients before clipping, let the scaler skip the update on overflow."""
+    un-scale the gradients before clipping, let the scaler skip the update on overflow.  An optimizer built with
+    `skip_nonfinite` skips a non-finite update on the device instead (no new argument: the step follows the optimizer); the
+    two together are refused — two skipping mechanisms would disagree about the step counters."""
     x, x_lengths, y, y_lengths, speaker_ids = batch
-    optimizer.zero_grad()
     flat = getattr(optimizer, "_optim", optimizer)
+    if scaler is not None and getattr(flat, "guard", None) is not None:
+        raise ValueError("train_batch: a GradScaler (scaler=...) together with an optimizer built with skip_nonfinite=True: "
+                         "the scaler already skips non-finite updates; use one of the two")
+    optimizer.zero_grad()
     with zero_scope(y.device):          # the step's atomically-accumulated temporaries share one zero fill
         (z, z_m, z_logs, logdet, z_mask), _, (_attn, logw, logw_) = model(x, x_lengths, y, y_lengths, g=speaker_ids)
         loss = mle_loss(z, z_m, z_logs, logdet, z_mask) + duration_loss(logw, logw_, x_lengths)
@@ -133,8 +149,9 @@ def _accumulate(model, optimizer, batches, reducer=None, reuse_packs: bool = Tru
 
 
 def _scale_clip_per_tensor(parameters, scale: float, clip_value: float) -> None:
-    """The general path of utils.clip_grad_value_ (a gradient replaced by a foreign tensor) for an accumulated gradient."""
-    sumsq = None
+    """The general path of utils.clip_grad_value_ (a gradient replaced by a foreign tensor) for an accumulated gradient; with
+    the owning optimizer's `skip_nonfinite`, every launch accumulates into its guard flag."""
+    sumsq = guard = None
     for p in parameters:
         if p.grad is None:
             continue
@@ -144,7 +161,12 @@ def _scale_clip_per_tensor(parameters, scale: float, clip_value: float) -> None:
             p.grad.data = g
         if sumsq is None:
             sumsq = torch.zeros(1, device=g.device, dtype=torch.float32)
-        call("glowtts_clip_grad_value_scaled", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq))
+            owner = getattr(p, "_glowtts_flat_owner", None)
+            guard = getattr(owner() if owner is not None else None, "guard", None)
+        if guard is not None:
+            call("glowtts_clip_grad_value_guarded", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq), ptr(guard))
+        else:
+            call("glowtts_clip_grad_value_scaled", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq))
 
 
 def train_batches(model, optimizer, batches, grad_clip: float, reducer=None, *, reuse_packs: bool = True) -> torch.Tensor:
@@ -179,6 +201,10 @@ class GraphedTrainStep:
     learning rate) from device memory, so one captured graph is valid for every later step; replay removes the host
     launch cost of the ~1 400 kernels of a step.  Batches must keep the shapes of `example_batch` (the reference's
     collate pads to the longest utterance of each batch, so a production loop keeps one graph per padded shape).
+
+    With an optimizer built with `skip_nonfinite` the guarded clip and Adam/Noam kernels are what `train_batch` launches, so
+    they are what is captured; `__call__` still advances the host mirror with every replay, whether the device applied the
+    update or skipped it, and `optimizer.sync_from_device()` is the reconciliation (call it wherever the host reads the loss).
     """
 
     def __init__(self, model, optimizer, grad_clip: float, example_batch, warmup: int = 2):
@@ -207,7 +233,8 @@ class GraphedTrainStep:
 
 
 def train_step(global_step: int, epoch: int, model, optimizer, config, train_loader, fp16_run: bool = False,
-               scaler=None, reducer=None, on_loss: typing.Optional[typing.Callable] = None, accum_steps: int = 1) -> int:
+               scaler=None, reducer=None, on_loss: typing.Optional[typing.Callable] = None, accum_steps: int = 1,
+               skip_nonfinite: bool = False) -> int:
     """Same signature and return value as the reference's `train_step` (train.py:91-100).
 
     `fp16_run` (reference train.py:116-121, 133-141: `autocast()` + GradScaler) selects the reduced-precision form of THIS
@@ -218,7 +245,14 @@ def train_step(global_step: int, epoch: int, model, optimizer, config, train_loa
 
     `accum_steps` (not part of the reference signature): loader batches per update.  N > 1 groups the batches N at a time into one
     `train_batches` update (a tail of m < N batches at the end of the epoch makes one update averaged over m); `global_step`
-    counts updates, `on_loss` receives the mean over updates.  Not combined with a GradScaler."""
+    counts updates, `on_loss` receives the mean over updates.  Not combined with a GradScaler.
+
+    `skip_nonfinite` (not part of the reference signature): the optimizer must have been built with
+    `optimize.Adam(..., skip_nonfinite=True)`; an update whose gradient holds a NaN or an Inf is then skipped on the device
+    (parameters, moments, Adam step, Noam step and rate stand still) and the epoch goes on.  At the epoch's one sync point
+    `optimizer.sync_from_device()` reconciles the host's step mirror, `on_loss` receives the mean over the FINITE losses, a
+    warning tells how many updates were skipped, and an epoch in which every update was skipped raises RuntimeError.
+    `global_step` counts update attempts as before.  Not combined with a GradScaler."""
     from .dataset import DeviceBatches
 
     accum_steps = int(accum_steps)
@@ -227,6 +261,14 @@ def train_step(global_step: int, epoch: int, model, optimizer, config, train_loa
     if accum_steps > 1 and scaler is not None:
         raise ValueError("train_step: accum_steps > 1 together with a GradScaler (scaler=...) is not supported; "
                          "fp16_run without a scaler (bf16 tensors need no loss scaling) is")
+    guarded = getattr(getattr(optimizer, "_optim", optimizer), "guard", None) is not None
+    if skip_nonfinite and not guarded:
+        raise ValueError("train_step: skip_nonfinite=True needs an optimizer built with the option: "
+                         "optimize.Adam(params, scheduler, dim_model, ..., skip_nonfinite=True)")
+    if guarded and scaler is not None:
+        raise ValueError("train_step: a GradScaler (scaler=...) together with an optimizer built with skip_nonfinite=True: "
+                         "the scaler already skips non-finite updates; use one of the two")
+    skipped_before = optimizer.sync_from_device()["skipped"] if guarded and hasattr(optimizer, "sync_from_device") else 0
 
     model.train()
     bare = model.module if hasattr(model, "module") else model
@@ -261,6 +303,18 @@ def train_step(global_step: int, epoch: int, model, optimizer, config, train_loa
             decoder.io_bf16 = before
         for m, b in zip(mha, mha_before):
             m.bf16_mma = b
-    if losses and on_loss is not None:
+    if losses and guarded and hasattr(optimizer, "sync_from_device"):
+        stacked = torch.stack(losses)
+        finite = torch.isfinite(stacked)
+        mean = torch.where(finite, stacked, torch.zeros_like(stacked)).sum() / finite.sum().clamp(min=1)
+        skipped = optimizer.sync_from_device()["skipped"] - skipped_before       # the epoch's sync point: counters, then the loss
+        if skipped:
+            _LOGGER.warning("Epoch %s: %s of %s update(s) skipped (non-finite gradient)", epoch, skipped, len(losses))
+        if skipped >= len(losses):
+            raise RuntimeError(f"train_step: every update of epoch {epoch} ({len(losses)}) had a non-finite gradient and was "
+                               "skipped; the model is not training")
+        if on_loss is not None:
+            on_loss(epoch, float(mean), global_step)
+    elif losses and on_loss is not None:
         on_loss(epoch, float(torch.stack(losses).mean()), global_step)   # ONE sync per epoch
     return global_step

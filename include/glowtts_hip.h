@@ -761,13 +761,35 @@ int glowtts_span_logw(const int32_t *first, const int32_t *t_x, float *logw_, in
  * adam : state[0] = Adam step t (float, >= 1 at the call), state[1] = Noam step_num; the learning rate
  *        lr * dim_model^-0.5 * min(s^-0.5, s * warmup^-1.5) (or `lr` if warmup <= 0) is computed ON DEVICE from
  *        state so a captured graph replays with the right rate; torch.optim.Adam arithmetic (no amsgrad/decay).
- * adam_advance: state[0] += 1; state[1] += 1; state[2] = learning rate of the NEXT update (optimize.py:43-48) */
+ * adam_advance: state[0] += 1; state[1] += 1; state[2] = learning rate of the NEXT update (optimize.py:43-48)
+ *
+ * `_guarded` forms: an update whose gradient holds a NaN or an Inf is skipped ON DEVICE — no host read, graph-capturable.  They
+ * stand in for the skip of GradScaler.step (train.py:133-141) in runs without a scaler.  guard is a device float[4]:
+ *        guard[0] "bad" flag of the pending update (0 clean, non-zero: a non-finite element was seen),
+ *        guard[1] updates skipped in total, guard[2] updates skipped consecutively up to now, guard[3] updates applied
+ *        (counters are floats like `state`, exact to 2^24).
+ * clip_guarded : clip_scaled (utils.py:118-132) + an exponent-bit test of every x = g * scale; a workgroup that saw a
+ *        non-finite x stores guard[0] = 1, a clean pass leaves guard[0] alone (several launches accumulate into one flag).  The
+ *        flag is per ELEMENT, not isfinite(sumsq): sumsq depends on the order of its atomics and can overflow over finite
+ *        elements.  Clean gradient: g equals clip_scaled's (scale != 1) and clip's (scale == 1) bit for bit.
+ * adam_guarded : adam (optimize.py:50-55) behind `if (guard[0] != 0) return`: a skipped update reads and writes nothing of
+ *        p, m, v; a clean one equals glowtts_adam_noam bit for bit.  The flag is PRODUCED by clip_guarded.
+ * adam_advance_guarded : clean — adam_advance (optimize.py:43-64), guard[3] += 1, guard[2] = 0; bad — state[0..3] untouched
+ *        (t, the Noam step, the next rate and a pending imposed rate stand still), guard[1] += 1, guard[2] += 1.
+ *        Either way guard[0] = 0 last. */
 int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state, float lr,
                       float beta1, float beta2, float eps, float dim_model, float warmup,
                       glowtts_stream_t stream);
 int glowtts_adam_advance(float *state, float lr, float dim_model, float warmup, glowtts_stream_t stream);
+int glowtts_clip_grad_value_guarded(float *g, int64_t n, float scale, float clip, float *sumsq, float *guard,
+                                    glowtts_stream_t stream);
+int glowtts_adam_noam_guarded(float *p, const float *g, float *m, float *v, int64_t n, const float *state,
+                              const float *guard, float lr, float beta1, float beta2, float eps, float dim_model,
+                              float warmup, glowtts_stream_t stream);
+int glowtts_adam_advance_guarded(float *state, float *guard, float lr, float dim_model, float warmup,
+                                 glowtts_stream_t stream);
 
 #ifdef __cplusplus
 }

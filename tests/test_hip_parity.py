@@ -289,7 +289,8 @@ def test_invconv_golden(G, name, n_split):
 @pytest.mark.parametrize("b,c,t,n_split", [(3, 8, 37, 4), (2, 8, 64, 2), (4, 160, 100, 4), (32, 160, 400, 4)])
 def test_actnorm_invconv_fused_vs_separate_and_oracle(G, b, c, t, n_split):
     """FlowSpecDecoder runs flows 3i, 3i+1 as ONE kernel each way (ops.ActNormInvConvFn); it must equal the two
-    separate flows (golden-pinned above) and the oracle's composition (reference layers.py:196-197, 247-272)."""
+    separate flows (golden-pinned above) and the oracle's composition (reference layers.py:196-197, 247-272).
+    The fused kernels alone, through the C ABI against fp64 at their dispatch edges: tests/test_flow_kernels.py."""
     from oracle import glow_oracle as O
 
     torch.manual_seed(b * 1000 + c + t)

@@ -6,6 +6,8 @@
 //                                                                  counter, so the whole step is hipGraph-capturable
 //   the same clip / Adam / Noam tail behind a device flag          (train.py:133-141: GradScaler.step's skip) — an update whose
 //                                                                  gradient holds a NaN or an Inf is skipped without a host read
+//   an exponential moving average of the parameters, kept by the   (no reference counterpart) — one more stream in and out of the
+//   Adam/Noam pass, and the exchange of two flat buffers             update kernel instead of a second pass over p
 #include "common.hpp"
 
 namespace glowtts {
@@ -285,10 +287,14 @@ __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model
     return (float)((double)lr * (1.0 / sqrt((double)dim_model)) * (a < b ? a : b));
 }
 
-template <int V>
+// EMA: the same pass also moves an average e of the parameters towards the NEW p, e += a (p_new - e) — the difference form: the
+// increment is formed from a small number, so fp32 holds it where d e + (1 - d) p would round 1 - d away.  The plain instantiations
+// (EMA = false) are the code they were before the flag existed.
+template <int V, bool EMA = false>
 __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                             float *__restrict__ v, long nv, const float *__restrict__ state, float lr, float b1,
-                                            float b2, float eps, float dim_model, float warmup) {
+                                            float b2, float eps, float dim_model, float warmup, float *__restrict__ e = nullptr,
+                                            float a = 0.f) {
     // torch.optim.Adam (no amsgrad, no weight decay): step_size = lr_t / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
     const float t = state[0];
     // state[3] > 0: a learning rate imposed for this one update (a resumed optimizer applies the rate stored in its
@@ -303,16 +309,20 @@ __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *
         Vec<V> gv = Vec<V>::load(g + i * V);
         Vec<V> mv = Vec<V>::load(m + i * V);
         Vec<V> vv = Vec<V>::load(v + i * V);
+        Vec<V> ev;
+        if constexpr (EMA) ev = Vec<V>::load(e + i * V);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             mv[j] = b1 * mv[j] + (1.0f - b1) * gv[j];
             vv[j] = b2 * vv[j] + (1.0f - b2) * gv[j] * gv[j];
             const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
             pv[j] -= step_size * (mv[j] / denom);
+            if constexpr (EMA) ev[j] += a * (pv[j] - ev[j]);
         }
         pv.store(p + i * V);
         mv.store(m + i * V);
         vv.store(v + i * V);
+        if constexpr (EMA) ev.store(e + i * V);
     }
 }
 
@@ -333,6 +343,41 @@ __global__ __launch_bounds__(256) void adam_guarded_kernel(float *__restrict__ p
                                                            float warmup) {
     if (guard[0] != 0.f) return;
     adam_update<V>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup);
+}
+
+// Weight of the new parameters in the average for THIS update: ema_rate = 1 - decay, or with the warm-up max(ema_rate, 9 / (10 + k))
+// — the (1 + k) / (10 + k) decay ramp of the usual EMA warm-up — where k = state[0] - ema_t0 counts the averaged updates so far
+// (0 for the first).  k comes from the device's Adam step, which stands still over a skipped update, so a captured graph replays
+// with the right weight and there is no state of the average's own.  fp64 and one rounding, like noam_rate.
+__device__ __forceinline__ float ema_weight(float t, float ema_rate, int ema_warm, float ema_t0) {
+    if (!ema_warm) return ema_rate;
+    const double k = (double)t - (double)ema_t0;
+    const double w = 9.0 / (10.0 + (k > 0.0 ? k : 0.0));
+    return (float)((double)ema_rate > w ? (double)ema_rate : w);
+}
+
+// The update of adam_kernel (guard == nullptr) or adam_guarded_kernel (guard != nullptr: a set flag makes the whole grid leave
+// before it has read or written anything of p, m, v or e) with the average e carried along; p, m, v come out as from those kernels.
+template <int V>
+__global__ __launch_bounds__(256) void adam_ema_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                       float *__restrict__ v, float *__restrict__ e, long nv,
+                                                       const float *__restrict__ state, const float *__restrict__ guard, float lr,
+                                                       float b1, float b2, float eps, float dim_model, float warmup,
+                                                       float ema_rate, int ema_warm, float ema_t0) {
+    if (guard != nullptr && guard[0] != 0.f) return;
+    adam_update<V, true>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup, e,
+                         ema_weight(state[0], ema_rate, ema_warm, ema_t0));
+}
+
+// a <-> b in one pass (FlatAdam.swap_ema: the averaged weights change places with the raw ones, no pointer moves)
+template <int V>
+__global__ __launch_bounds__(256) void swap_kernel(float *__restrict__ a, float *__restrict__ b, long nv) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
+        const Vec<V> av = Vec<V>::load(a + i * V);
+        const Vec<V> bv = Vec<V>::load(b + i * V);
+        bv.store(a + i * V);
+        av.store(b + i * V);
+    }
 }
 
 __global__ void adam_advance_kernel(float *state, float lr, float dim_model, float warmup) {
@@ -565,6 +610,35 @@ extern "C" int glowtts_adam_advance_guarded(float *state, float *guard, float lr
     GLOWTTS_CHECK_ARG(state && guard, "glowtts_adam_advance_guarded: null pointer");
     hipLaunchKernelGGL(adam_advance_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, guard, lr, dim_model, warmup);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance_guarded");
+}
+
+extern "C" int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *v, float *e, int64_t n, const float *state,
+                                     const float *guard, float lr, float beta1, float beta2, float eps, float dim_model,
+                                     float warmup, float ema_rate, int ema_warm, float ema_t0, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(p && g && m && v && e && state, "glowtts_adam_noam_ema: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam_ema: negative size");
+    GLOWTTS_CHECK_ARG(ema_rate > 0.f && ema_rate < 1.f, "glowtts_adam_noam_ema: ema_rate (1 - decay) must lie in (0, 1)");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((n & 3) == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e))
+        hipLaunchKernelGGL((adam_ema_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, p, g, m, v, e, (long)(n / 4), state, guard, lr, beta1, beta2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
+    else
+        hipLaunchKernelGGL((adam_ema_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, e, (long)n, state, guard, lr, beta1, beta2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_ema");
+}
+
+extern "C" int glowtts_swap_f32(float *a, float *b, int64_t n, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(a && b, "glowtts_swap_f32: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0 && n <= INT64_MAX / 4, "glowtts_swap_f32: bad size");
+    const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4u;
+    GLOWTTS_CHECK_ARG(ua + bytes <= ub || ub + bytes <= ua || n == 0, "glowtts_swap_f32: the buffers overlap");
+    if (n == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if ((n & 3) == 0 && aligned16(a) && aligned16(b))
+        hipLaunchKernelGGL((swap_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, a, b, (long)(n / 4));
+    else
+        hipLaunchKernelGGL((swap_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, a, b, (long)n);
+    GLOWTTS_LAUNCH_CHECK("glowtts_swap_f32");
 }
 
 // ------------------------------------------------------------------------------------------------------------

@@ -94,6 +94,10 @@ _SIGNATURES = {
     "glowtts_clip_grad_value_guarded": [_P, _L, _F, _F, _P, _P],
     "glowtts_adam_noam_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F],
     "glowtts_adam_advance_guarded": [_P, _P, _F, _F, _F],
+    # the Adam/Noam update that also keeps an exponential moving average of the parameters (guard may be NULL), and the exchange
+    # of two flat buffers behind FlatAdam.swap_ema
+    "glowtts_adam_noam_ema": [_P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F, _F, _I, _F],
+    "glowtts_swap_f32": [_P, _P, _L],
     # whole WN stack per call (csrc/wn_stack.hip); the first argument is a HOST array of WnLayer
     "glowtts_wn_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I],
     "glowtts_wn_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -4,10 +4,13 @@ restructured for MI355X: every parameter, gradient and moment lives in ONE flat 
   * `clip_grad_value_` is one streaming kernel instead of 519 `.item()` host syncs (reference utils.py:126-128),
   * the update is one streaming kernel over 4 x 114.5 MB (12 blocks) instead of ~519 x 4 small launches,
   * gradient buckets for data-parallel all-reduce are plain slices of the flat gradient buffer (parallel.py),
-  * the learning rate is derived on device from a step counter, so a captured hipGraph replays correctly.
+  * the learning rate is derived on device from a step counter, so a captured hipGraph replays correctly,
+  * an exponential moving average of the parameters (`ema_decay=`) is one more flat buffer streamed through the same update
+    kernel: no second pass over the parameters, no extra launch, no host work on the step path.
 """
 from __future__ import annotations
 
+import contextlib
 import typing
 import weakref
 from operator import is_ as _is
@@ -29,10 +32,18 @@ class FlatAdam(torch.optim.Optimizer):
     consecutively, updates applied].  The flag is PRODUCED by the clip pass (`clip_grad_value_` here, `utils.clip_grad_value_`,
     both of `train`'s routes): `step()` skips exactly when a clip since the last step saw a non-finite element, so a caller
     who does not clip gets an unguarded update, as without the option.  The counters are not part of `state_dict()` (the file
-    format is the reference's): they restart at zero on resume."""
+    format is the reference's): they restart at zero on resume.
+
+    `ema_decay` (off by default; no reference counterpart): `flat_e`, one more flat buffer, holds an exponential moving average
+    of the parameters, e <- e + a (p_new - e), moved by the update kernel itself (glowtts_adam_noam_ema, include/glowtts_hip.h)
+    with a = 1 - decay, or with `ema_warmup` a = max(1 - decay, 9 / (10 + k)) for the k-th averaged update.  An update the
+    device skips (`skip_nonfinite`) leaves the average and its count alone.  `ema_state_dict` / `swap_ema` hand the averaged
+    weights out; `state_dict()` keeps torch's layout (checkpoint.py stores the average under keys of its own).  With the
+    option off nothing is allocated and nothing else is launched."""
 
     def __init__(self, params, lr=1.0, betas=(0.9, 0.98), eps=1e-9, dim_model: float = 0.0, warmup_steps: float = 0.0,
-                 base_lr: typing.Optional[float] = None, skip_nonfinite: bool = False):
+                 base_lr: typing.Optional[float] = None, skip_nonfinite: bool = False,
+                 ema_decay: typing.Optional[float] = None, ema_warmup: bool = False):
         params = [p for p in params]
         # the group carries every key torch.optim.Adam's does (amsgrad, weight_decay, foreach, ... at their defaults), so
         # state_dict() has torch's layout for this torch version and the reference loads it unchanged
@@ -41,9 +52,17 @@ class FlatAdam(torch.optim.Optimizer):
         self.base_lr = float(lr if base_lr is None else base_lr)
         self.dim_model, self.warmup = float(dim_model), float(warmup_steps)
         self.guard: typing.Optional[torch.Tensor] = None
+        self.flat_e: typing.Optional[torch.Tensor] = None
+        self.ema_decay: typing.Optional[float] = None
+        self.ema_warmup = False
+        self._ema_rate, self._ema_t0, self._ema_swapped = 0.0, 0.0, False
+        if ema_decay is not None:
+            _check_decay(ema_decay)
         self._build_flat()
         if skip_nonfinite:
             self.enable_skip_nonfinite()
+        if ema_decay is not None:
+            self.enable_ema(ema_decay, ema_warmup)
 
     # -- layout -------------------------------------------------------------------------------------------------
     def _build_flat(self):
@@ -90,6 +109,103 @@ class FlatAdam(torch.optim.Optimizer):
     def slices(self):
         """(offset, numel) of every parameter inside the flat buffers, in construction order."""
         return [(o, p.numel()) for p, o in zip(self._params, self.offsets)]
+
+    # -- exponential moving average of the parameters -----------------------------------------------------------
+    def enable_ema(self, decay: float, warmup: bool = False, num_updates: int = 0) -> None:
+        """Switch the average on (once: a second call raises): `flat_e` starts as a copy of `flat_p`, padding included, and the
+        updates from now on move it.  `num_updates`: averaged updates already behind this average (a resumed run) — the warm-up
+        continues from there.  Reads the device's Adam step once; the count is kept as the step the average started at, so no
+        state of its own lives on the device.
+
+        Call it AFTER a data-parallel broadcast of the parameters (parallel.FlowBlockReducer.broadcast_parameters): the ranks'
+        averages start from the copy made here and then see the same updates, so they stay bit-equal only if the parameters
+        were already the same when it was made."""
+        if self.flat_e is not None:
+            raise RuntimeError("FlatAdam.enable_ema: the average is already on")
+        decay = _check_decay(decay)
+        num_updates = int(num_updates)
+        if num_updates < 0:
+            raise ValueError(f"FlatAdam.enable_ema: num_updates must be >= 0, got {num_updates}")
+        self.ema_decay, self.ema_warmup = decay, bool(warmup)
+        self._ema_rate = 1.0 - decay                        # fp64 here, rounded to fp32 once at the call (1 - fl32(decay) is not this)
+        self._ema_t0 = float(self.dev_state[0]) - num_updates
+        self.flat_e = self.flat_p.clone()
+
+    def _need_ema(self, who: str) -> None:
+        if self.flat_e is None:
+            raise RuntimeError(f"FlatAdam.{who}: the optimizer was built without ema_decay (enable_ema switches it on)")
+
+    def ema_num_updates(self) -> int:
+        """Updates the average has seen (ONE device read); an update the device skipped is not among them."""
+        self._need_ema("ema_num_updates")
+        return int(round(float(self.dev_state[0]) - self._ema_t0))
+
+    def _owned(self, tensor: torch.Tensor) -> typing.Optional[int]:
+        """Offset in the flat buffers of the parameter `tensor` is a view of (a state_dict entry shares its parameter's storage),
+        None for anything else."""
+        by_offset = getattr(self, "_numel_at", None)
+        if by_offset is None:
+            by_offset = self._numel_at = {o: p.numel() for p, o in zip(self._params, self.offsets)}
+        if tensor.device != self.flat_p.device or tensor.dtype != torch.float32 or tensor.numel() == 0:
+            return None
+        delta = tensor.data_ptr() - self.flat_p.data_ptr()
+        if delta < 0 or delta % 4 or by_offset.get(delta // 4) != tensor.numel():
+            return None
+        return delta // 4
+
+    def ema_state_dict(self, model) -> dict:
+        """`model.state_dict()` with every parameter this optimizer owns replaced by its averaged value (a clone); every other
+        entry (buffers, parameters of another optimizer) is copied.  Keys, their order and the shapes are the model's."""
+        self._need_ema("ema_state_dict")
+        averaged = self.flat_p if self._ema_swapped else self.flat_e          # inside swap_ema() the two have changed places
+        out = {}
+        for key, value in model.state_dict().items():
+            o = self._owned(value)
+            out[key] = (value if o is None else averaged[o:o + value.numel()].view(value.shape)).detach().clone()
+        return out
+
+    def load_ema_state_dict(self, model, averaged: dict, num_updates: typing.Optional[int] = None) -> None:
+        """The inverse of `ema_state_dict`: fill `flat_e` from `averaged` (entries of parameters this optimizer does not own are
+        ignored, a missing or mis-shaped one raises) and, if given, continue the count at `num_updates`."""
+        self._need_ema("load_ema_state_dict")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.load_ema_state_dict inside swap_ema()")
+        with torch.no_grad():
+            for key, value in model.state_dict().items():
+                o = self._owned(value)
+                if o is None:
+                    continue
+                if key not in averaged or tuple(averaged[key].shape) != tuple(value.shape):
+                    raise ValueError(f"averaged weights: no entry of shape {tuple(value.shape)} for {key}")
+                self.flat_e[o:o + value.numel()].copy_(averaged[key].reshape(-1))
+        if num_updates is not None:
+            self._ema_t0 = float(self.dev_state[0]) - int(num_updates)
+
+    @contextlib.contextmanager
+    def swap_ema(self):
+        """`with opt.swap_ema():` — the model runs on the averaged weights (validation, synthesis): `flat_p` and `flat_e` are
+        exchanged by one kernel on entry and again on exit; the parameters stay views of `flat_p`, so no pointer moves and no
+        module is touched.  Both exchanges call `convops.weights_changed()`: nothing packed from the other weights is reused.
+        Inside the scope `step()`, `enable_ema`, a nested `swap_ema()` and `checkpoint.save_checkpoint` raise; entering it inside
+        `convops.weights_unchanged()` raises."""
+        self._need_ema("swap_ema")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.swap_ema: already inside swap_ema()")
+        if weights_state.active:
+            raise RuntimeError("FlatAdam.swap_ema inside convops.weights_unchanged(): the scope must end before the weights change")
+        self._exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange()
+            self._ema_swapped = False
+
+    def _exchange(self) -> None:
+        from .convops import weights_changed
+
+        call("glowtts_swap_f32", ptr(self.flat_p), ptr(self.flat_e), self.numel_padded)
+        weights_changed()
 
     # -- torch.optim surface ------------------------------------------------------------------------------------
     def _grad_views(self):
@@ -138,6 +254,8 @@ class FlatAdam(torch.optim.Optimizer):
             raise NotImplementedError("FlatAdam.step: closures are not supported")
         if weights_state.active:                      # (convops.weights_unchanged: packed weights are being reused as they are)
             raise RuntimeError("FlatAdam.step inside convops.weights_unchanged(): the scope must end before the weights change")
+        if self._ema_swapped:
+            raise RuntimeError("FlatAdam.step inside swap_ema(): the parameters hold the averaged weights")
         if not self.grads_in_place():                 # a foreign hook may have replaced .grad: fold it back in
             views = self._grad_views()
             for i, (p, o) in enumerate(zip(self._params, self.offsets)):
@@ -148,6 +266,15 @@ class FlatAdam(torch.optim.Optimizer):
                     p.grad = views[i]
         g = self.param_groups[0]
         b1, b2 = g["betas"]
+        if self.flat_e is not None:                   # the same update with the average carried along; the advance is the usual one
+            call("glowtts_adam_noam_ema", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), ptr(self.flat_e),
+                 self.numel_padded, ptr(self.dev_state), ptr(self.guard), self.base_lr, float(b1), float(b2), float(g["eps"]),
+                 self.dim_model, self.warmup, self._ema_rate, int(self.ema_warmup), self._ema_t0)
+            if self.guard is not None:
+                call("glowtts_adam_advance_guarded", ptr(self.dev_state), ptr(self.guard), self.base_lr, self.dim_model, self.warmup)
+            else:
+                call("glowtts_adam_advance", ptr(self.dev_state), self.base_lr, self.dim_model, self.warmup)
+            return
         if self.guard is not None:
             call("glowtts_adam_noam_guarded", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
                  self.numel_padded, ptr(self.dev_state), ptr(self.guard), self.base_lr, float(b1), float(b2), float(g["eps"]),
@@ -161,7 +288,8 @@ class FlatAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         """torch.optim.Adam-compatible layout: state[i] = {step, exp_avg, exp_avg_sq} (what checkpoint.py:44 saves).  The
-        `skip_nonfinite` counters (`guard`) are not saved."""
+        `skip_nonfinite` counters (`guard`) are not saved, and neither is the averaged copy of the weights (`ema_state_dict`;
+        checkpoint.py writes it under keys of its own): the layout is torch's with the option on or off."""
         t = (self.dev_state[0] - 1.0).detach().cpu()        # ONE device read for the step every entry shares
         state = {}
         for i, (p, o) in enumerate(zip(self._params, self.offsets)):
@@ -183,6 +311,8 @@ class FlatAdam(torch.optim.Optimizer):
         with a warning."""
         st = d.get("state", {})
         saved_groups = d.get("param_groups", [])
+        # the average counts its updates from the device's Adam step, which this call may move: the count itself stays
+        ema_seen = self.ema_num_updates() if self.flat_e is not None else None
         if saved_groups and "params" in saved_groups[0]:
             n_saved = sum(len(g["params"]) for g in saved_groups)
             if n_saved != len(self._params):
@@ -217,6 +347,8 @@ class FlatAdam(torch.optim.Optimizer):
                     import warnings
                     warnings.warn("FlatAdam.load_state_dict: per-parameter steps differ; using the largest")
                 self.dev_state[0] = max(steps) + 1.0
+                if ema_seen is not None:
+                    self._ema_t0 = max(steps) + 1.0 - ema_seen
         for g_new, g in zip(d.get("param_groups", []), self.param_groups):
             for k in ("lr", "betas", "eps"):
                 if k in g_new:
@@ -232,12 +364,22 @@ class FlatAdam(torch.optim.Optimizer):
                 self.base_lr = lr
 
 
+def _check_decay(decay) -> float:
+    decay = float(decay)
+    if not 0.0 < decay < 1.0:
+        raise ValueError(f"ema_decay must lie strictly between 0 and 1, got {decay}")
+    return decay
+
+
 class Adam:
     """Reference surface (optimize.py:8-64): `Adam(params, scheduler, dim_model, warmup_steps, lr, betas, eps)` with
-    `.step() .zero_grad() .get_lr() .state_dict() .load_state_dict() .cur_lr .step_num ._optim`."""
+    `.step() .zero_grad() .get_lr() .state_dict() .load_state_dict() .cur_lr .step_num ._optim`.  Keyword-only additions:
+    `skip_nonfinite`, `ema_decay`, `ema_warmup` (FlatAdam); `enable_ema`, `ema_num_updates`, `ema_state_dict` and `swap_ema`
+    are FlatAdam's."""
 
     def __init__(self, params, scheduler, dim_model, warmup_steps: int = 4000, lr: float = 1e0,
-                 betas: typing.Tuple[float, float] = (0.9, 0.98), eps: float = 1e-9, *, skip_nonfinite: bool = False):
+                 betas: typing.Tuple[float, float] = (0.9, 0.98), eps: float = 1e-9, *, skip_nonfinite: bool = False,
+                 ema_decay: typing.Optional[float] = None, ema_warmup: bool = False):
         self.params = list(params)
         self.scheduler, self.dim_model, self.warmup_steps = scheduler, dim_model, warmup_steps
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -246,7 +388,7 @@ class Adam:
         noam = scheduler == "noam"
         self._optim = FlatAdam(self.params, lr=self.cur_lr, betas=betas, eps=eps, base_lr=lr,
                                dim_model=dim_model if noam else 0.0, warmup_steps=warmup_steps if noam else 0.0,
-                               skip_nonfinite=skip_nonfinite)
+                               skip_nonfinite=skip_nonfinite, ema_decay=ema_decay, ema_warmup=ema_warmup)
 
     def _get_lr_scale(self):
         if self.scheduler == "noam":
@@ -271,6 +413,18 @@ class Adam:
 
     def zero_grad(self):
         self._optim.zero_grad()
+
+    def enable_ema(self, decay: float, warmup: bool = False, num_updates: int = 0) -> None:
+        self._optim.enable_ema(decay, warmup, num_updates)
+
+    def ema_num_updates(self) -> int:
+        return self._optim.ema_num_updates()
+
+    def ema_state_dict(self, model) -> dict:
+        return self._optim.ema_state_dict(model)
+
+    def swap_ema(self):
+        return self._optim.swap_ema()
 
     def sync_from_device(self) -> typing.Dict[str, int]:
         """ONE device-to-host copy of the device's step state and the `skip_nonfinite` counters; sets `step_num`, `cur_lr` and

@@ -13,6 +13,10 @@ all-reduce compute (DistributedDataParallel, reference __main__.py:268-271) on o
 Non-finite updates (`skip_nonfinite=`, an optimizer built with `optimize.Adam(..., skip_nonfinite=True)`): the clip pass flags a
 gradient that holds a NaN or an Inf and the Adam/Noam kernels skip that update on the device — no host read on the step path;
 the epoch's one synchronisation also reads the skip counters (`Adam.sync_from_device`).
+
+Averaged weights (`ema_decay=`, an optimizer built with `optimize.Adam(..., ema_decay=0.999)`): the Adam/Noam kernel also moves an
+exponential moving average of the parameters — nothing is added to the step path but one buffer streamed through that kernel;
+checkpoints carry the average (`"model_ema"`), `optimizer.swap_ema()` runs the model on it.
 """
 from __future__ import annotations
 
@@ -34,12 +38,15 @@ _LOGGER = logging.getLogger("glow_tts_train")
 
 
 def train(train_loader, config, model_dir: Path, model=None, optimizer=None, global_step: int = 1,
-          checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1, skip_nonfinite: bool = False):
+          checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1, skip_nonfinite: bool = False,
+          ema_decay: typing.Optional[float] = None, ema_warmup: bool = False):
     """Epoch loop of the reference (train.py:19-88): seed, build or adopt model and optimizer, run `config.epochs`
     passes over `train_loader`, and on rank 0 write `checkpoint_<step>.pth` + `config_<step>.json` into `model_dir`
     every `checkpoint_epochs` epochs.  Returns the final global step.  `accum_steps`: loader batches per update (train_step).
     `skip_nonfinite`: skip updates whose gradient is not finite (train_step); an optimizer built here gets the option switched
-    on, one passed in must have been built with it."""
+    on, one passed in must have been built with it.  `ema_decay` / `ema_warmup`: keep an exponential moving average of the
+    weights (optimize.FlatAdam); an optimizer built here gets it switched on, one passed in is taken as it is.  The checkpoints
+    of an averaging optimizer carry the average."""
     from .checkpoint import Checkpoint, save_checkpoint
     from .models import setup_model
 
@@ -49,6 +56,8 @@ def train(train_loader, config, model_dir: Path, model=None, optimizer=None, glo
     assert model is not None and optimizer is not None
     if skip_nonfinite and built_here:
         optimizer._optim.enable_skip_nonfinite()
+    if ema_decay is not None and built_here:
+        optimizer._optim.enable_ema(ema_decay, ema_warmup)
     model_dir = Path(model_dir)
     for epoch in range(1, config.epochs + 1):
         started = time.perf_counter()

@@ -776,7 +776,17 @@ int glowtts_span_logw(const int32_t *first, const int32_t *t_x, float *logw_, in
  *        p, m, v; a clean one equals glowtts_adam_noam bit for bit.  The flag is PRODUCED by clip_guarded.
  * adam_advance_guarded : clean — adam_advance (optimize.py:43-64), guard[3] += 1, guard[2] = 0; bad — state[0..3] untouched
  *        (t, the Noam step, the next rate and a pending imposed rate stand still), guard[1] += 1, guard[2] += 1.
- *        Either way guard[0] = 0 last. */
+ *        Either way guard[0] = 0 last.
+ *
+ * adam_ema : an exponential moving average e of the parameters, kept by the update kernel (no reference counterpart: TTS trainers
+ *        average on the host or average checkpoints afterwards).  The update of adam (guard == NULL) or adam_guarded (guard != NULL:
+ *        a set guard[0] makes the grid leave before it reads or writes anything of p, m, v, e) and, on the same element in the same
+ *        pass, e += a (p_new - e); p, m, v come out bit for bit as from glowtts_adam_noam.  ema_rate = 1 - decay, formed by the
+ *        caller in fp64 and rounded once (1 - 0.99999f is already 0.14 % off), in (0, 1).  ema_warm == 0: a = ema_rate; ema_warm
+ *        != 0: a = max(ema_rate, 9 / (10 + k)), k = state[0] - ema_t0 the number of averaged updates so far (0 for the first), read
+ *        from device memory — a captured graph replays with the right weight, a skipped update does not count, and
+ *        adam_advance / adam_advance_guarded follow unchanged.  Elements with p = e = 0 and g = m = v = 0 stay exactly zero.
+ * swap_f32 : exchanges two equally long buffers in one pass; overlapping buffers are refused. */
 int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state, float lr,
@@ -790,6 +800,10 @@ int glowtts_adam_noam_guarded(float *p, const float *g, float *m, float *v, int6
                               float warmup, glowtts_stream_t stream);
 int glowtts_adam_advance_guarded(float *state, float *guard, float lr, float dim_model, float warmup,
                                  glowtts_stream_t stream);
+int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *v, float *e, int64_t n, const float *state,
+                          const float *guard, float lr, float beta1, float beta2, float eps, float dim_model, float warmup,
+                          float ema_rate, int ema_warm, float ema_t0, glowtts_stream_t stream);
+int glowtts_swap_f32(float *a, float *b, int64_t n, glowtts_stream_t stream);
 
 #ifdef __cplusplus
 }

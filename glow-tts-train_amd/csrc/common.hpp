@@ -6,6 +6,7 @@
 
 #include <atomic>
 #include <initializer_list>
+#include <type_traits>
 
 #include "glowtts_hip.h"
 
@@ -139,6 +140,17 @@ static inline bool can_vec4(int T, std::initializer_list<const void *> ptrs) {
     for (const void *p : ptrs)
         if (p && !aligned16(p)) return false;
     return true;
+}
+
+// The same decision for a FLAT buffer of n floats, taken once per launch: `launch(width, count)` is called with
+// std::integral_constant<int, 4> and n / 4 when n % 4 == 0 and every pointer is 16-B aligned (a null one counts as aligned), else
+// with <int, 1> and n — a generic lambda writes its launch line once and instantiates the kernel with `width`.
+template <class Launch>
+static inline void vec4_or_scalar(long n, std::initializer_list<const void *> ptrs, Launch &&launch) {
+    bool wide = (n & 3) == 0;
+    for (const void *p : ptrs) wide = wide && aligned16(p);
+    if (wide) launch(std::integral_constant<int, 4>{}, n / 4);
+    else launch(std::integral_constant<int, 1>{}, n);
 }
 
 // Dynamic-LDS limit of one kernel (`static LdsLimit x;` at the launch site): hipFuncSetAttribute is per DEVICE, so the

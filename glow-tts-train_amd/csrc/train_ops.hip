@@ -8,6 +8,9 @@
 //                                                                  gradient holds a NaN or an Inf is skipped without a host read
 //   an exponential moving average of the parameters, kept by the   (no reference counterpart) — one more stream in and out of the
 //   Adam/Noam pass, and the exchange of two flat buffers             update kernel instead of a second pass over p
+// The tail is ONE kernel per pass — clip_kernel<V, SCALE, GUARD>, adam_kernel<V, GUARD, EMA>, adam_advance_kernel — behind eight
+// entry points: an option is a compile-time flag of the pass it belongs to, so the default forms carry none of its instructions.
+// The flat kernels choose 16-byte or scalar access per launch through vec4_or_scalar (common.hpp).
 #include "common.hpp"
 
 namespace glowtts {
@@ -189,68 +192,20 @@ __global__ __launch_bounds__(256) void span_logw_kernel(const int *__restrict__ 
 // ------------------------------------------------------------------------------------------------------------
 // Reducing kernels end in one same-address atomic per workgroup, and those retire serially in L2 (~13 ns each): they
 // run on a small grid (reduce_grid) and get their memory-level parallelism from 4 independent vector loads per thread.
-template <int V>
-__global__ __launch_bounds__(256) void clip_kernel(float *__restrict__ g, long nv, float clip, float *__restrict__ sumsq) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const long stride = (long)gridDim.x * 256;
-    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < nv; i0 += 4 * stride) {
-        Vec<V> gv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            gv[u] = (i0 + u * stride < nv) ? Vec<V>::load(g + (i0 + u * stride) * V) : Vec<V>::zero();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                s += gv[u][j] * gv[u][j];
-                gv[u][j] = fminf(fmaxf(gv[u][j], -clip), clip);
-            }
-            if (i0 + u * stride < nv) gv[u].store(g + (i0 + u * stride) * V);
-        }
-    }
-    s = block_sum_256(s, red);
-    if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
-}
-
-// The same pass over a gradient that is the SUM of several micro-batches' gradients (train.train_batches): x = g * scale first
-// (scale = 1 / micro-batches, the mean an AVG all-reduce over as many ranks would leave), then the norm and the clamp of x — the
-// averaging costs no pass of its own over the flat buffer.  scale == 1 reproduces clip_kernel bit for bit.
-template <int V>
-__global__ __launch_bounds__(256) void clip_scaled_kernel(float *__restrict__ g, long nv, float scale, float clip,
-                                                          float *__restrict__ sumsq) {
-    __shared__ float red[4];
-    float s = 0.f;
-    const long stride = (long)gridDim.x * 256;
-    for (long i0 = (long)blockIdx.x * 256 + threadIdx.x; i0 < nv; i0 += 4 * stride) {
-        Vec<V> gv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            gv[u] = (i0 + u * stride < nv) ? Vec<V>::load(g + (i0 + u * stride) * V) : Vec<V>::zero();
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float x = gv[u][j] * scale;
-                s += x * x;
-                gv[u][j] = fminf(fmaxf(x, -clip), clip);
-            }
-            if (i0 + u * stride < nv) gv[u].store(g + (i0 + u * stride) * V);
-        }
-    }
-    s = block_sum_256(s, red);
-    if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
-}
-
-// clip_scaled_kernel that also tells whether the gradient may be applied at all (guard[0], include/glowtts_hip.h): fmaxf(NaN, -clip)
-// is -clip and an Inf clamps to +-clip, so after this pass a poisoned gradient looks like any other.  The test is on the exponent
+//
+// One body behind the three clip entry points; the flags are compile-time, so a form carries none of the others' instructions.
+// SCALE: the gradient is the SUM of several micro-batches' gradients (train.train_batches): x = g * scale first (scale = 1 /
+// micro-batches, the mean an AVG all-reduce over as many ranks would leave), then the norm and the clamp of x — the averaging costs
+// no pass of its own over the flat buffer.  scale == 1 reproduces the unscaled form bit for bit.
+// GUARD: the pass also tells whether the gradient may be applied at all (guard[0], include/glowtts_hip.h): fmaxf(NaN, -clip) is
+// -clip and an Inf clamps to +-clip, so after this pass a poisoned gradient looks like any other.  The test is on the exponent
 // bits of every x = g * scale, not on sumsq: the sum depends on the order of the atomics and can overflow over finite elements,
 // and data-parallel ranks holding the same reduced gradient must reach the same decision.  A workgroup that saw a non-finite x
 // stores 1 (every writer stores the same value: no atomic); a clean pass leaves guard[0] as it found it, so several launches
-// (one per gradient tensor) accumulate into one flag.  On a clean gradient g and sumsq are clip_scaled_kernel's, bit for bit.
-template <int V>
-__global__ __launch_bounds__(256) void clip_guarded_kernel(float *__restrict__ g, long nv, float scale, float clip,
-                                                           float *__restrict__ sumsq, float *__restrict__ guard) {
+// (one per gradient tensor) accumulate into one flag.  On a clean gradient g and sumsq are the unguarded form's, bit for bit.
+template <int V, bool SCALE, bool GUARD>
+__global__ __launch_bounds__(256) void clip_kernel(float *__restrict__ g, long nv, float scale, float clip,
+                                                   float *__restrict__ sumsq, float *__restrict__ guard) {
     __shared__ float red[4];
     float s = 0.f;
     int bad = 0;
@@ -264,8 +219,9 @@ __global__ __launch_bounds__(256) void clip_guarded_kernel(float *__restrict__ g
         for (int u = 0; u < 4; ++u) {
 #pragma unroll
             for (int j = 0; j < V; ++j) {
-                const float x = gv[u][j] * scale;
-                bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;     // exponent all ones: Inf or NaN
+                float x = gv[u][j];
+                if constexpr (SCALE) x *= scale;
+                if constexpr (GUARD) bad |= (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u;     // exponent all ones: Inf or NaN
                 s += x * x;
                 gv[u][j] = fminf(fmaxf(x, -clip), clip);
             }
@@ -274,8 +230,10 @@ __global__ __launch_bounds__(256) void clip_guarded_kernel(float *__restrict__ g
     }
     s = block_sum_256(s, red);
     if (threadIdx.x == 0 && sumsq) atomicAdd(sumsq, s);
-    const int any_bad = __syncthreads_or(bad);
-    if (threadIdx.x == 0 && any_bad) guard[0] = 1.0f;
+    if constexpr (GUARD) {
+        const int any_bad = __syncthreads_or(bad);
+        if (threadIdx.x == 0 && any_bad) guard[0] = 1.0f;
+    }
 }
 
 __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model, float warmup) {
@@ -288,13 +246,12 @@ __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model
 }
 
 // EMA: the same pass also moves an average e of the parameters towards the NEW p, e += a (p_new - e) — the difference form: the
-// increment is formed from a small number, so fp32 holds it where d e + (1 - d) p would round 1 - d away.  The plain instantiations
-// (EMA = false) are the code they were before the flag existed.
-template <int V, bool EMA = false>
+// increment is formed from a small number, so fp32 holds it where d e + (1 - d) p would round 1 - d away.  With EMA = false e and
+// a are not touched, and the code is what it was before the flag existed.
+template <int V, bool EMA>
 __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                             float *__restrict__ v, long nv, const float *__restrict__ state, float lr, float b1,
-                                            float b2, float eps, float dim_model, float warmup, float *__restrict__ e = nullptr,
-                                            float a = 0.f) {
+                                            float b2, float eps, float dim_model, float warmup, float *__restrict__ e, float a) {
     // torch.optim.Adam (no amsgrad, no weight decay): step_size = lr_t / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
     const float t = state[0];
     // state[3] > 0: a learning rate imposed for this one update (a resumed optimizer applies the rate stored in its
@@ -326,25 +283,6 @@ __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *
     }
 }
 
-template <int V>
-__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                   float *__restrict__ v, long nv, const float *__restrict__ state, float lr,
-                                                   float b1, float b2, float eps, float dim_model, float warmup) {
-    adam_update<V>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup);
-}
-
-// The same update behind the flag the guarded clip pass left (guard[0] != 0: a non-finite gradient element was seen): the whole
-// grid leaves before it has read or written anything of p, m or v.
-template <int V>
-__global__ __launch_bounds__(256) void adam_guarded_kernel(float *__restrict__ p, const float *__restrict__ g,
-                                                           float *__restrict__ m, float *__restrict__ v, long nv,
-                                                           const float *__restrict__ state, const float *__restrict__ guard,
-                                                           float lr, float b1, float b2, float eps, float dim_model,
-                                                           float warmup) {
-    if (guard[0] != 0.f) return;
-    adam_update<V>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup);
-}
-
 // Weight of the new parameters in the average for THIS update: ema_rate = 1 - decay, or with the warm-up max(ema_rate, 9 / (10 + k))
 // — the (1 + k) / (10 + k) decay ramp of the usual EMA warm-up — where k = state[0] - ema_t0 counts the averaged updates so far
 // (0 for the first).  k comes from the device's Adam step, which stands still over a skipped update, so a captured graph replays
@@ -356,17 +294,21 @@ __device__ __forceinline__ float ema_weight(float t, float ema_rate, int ema_war
     return (float)((double)ema_rate > w ? (double)ema_rate : w);
 }
 
-// The update of adam_kernel (guard == nullptr) or adam_guarded_kernel (guard != nullptr: a set flag makes the whole grid leave
-// before it has read or written anything of p, m, v or e) with the average e carried along; p, m, v come out as from those kernels.
-template <int V>
-__global__ __launch_bounds__(256) void adam_ema_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
-                                                       float *__restrict__ v, float *__restrict__ e, long nv,
-                                                       const float *__restrict__ state, const float *__restrict__ guard, float lr,
-                                                       float b1, float b2, float eps, float dim_model, float warmup,
-                                                       float ema_rate, int ema_warm, float ema_t0) {
-    if (guard != nullptr && guard[0] != 0.f) return;
-    adam_update<V, true>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup, e,
-                         ema_weight(state[0], ema_rate, ema_warm, ema_t0));
+// One kernel behind the three Adam/Noam entry points, flags compile-time as in clip_kernel.
+// GUARD: the update stands behind the flag the guarded clip pass left (guard[0] != 0: a non-finite gradient element was seen) — the
+// whole grid leaves before it has read or written anything of p, m, v or e.
+// EMA: the average e is carried along (adam_update); p, m and v come out as without it.
+template <int V, bool GUARD, bool EMA>
+__global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
+                                                   float *__restrict__ v, float *__restrict__ e, long nv,
+                                                   const float *__restrict__ state, const float *__restrict__ guard, float lr,
+                                                   float b1, float b2, float eps, float dim_model, float warmup, float ema_rate,
+                                                   int ema_warm, float ema_t0) {
+    if constexpr (GUARD)
+        if (guard[0] != 0.f) return;
+    float a = 0.f;
+    if constexpr (EMA) a = ema_weight(state[0], ema_rate, ema_warm, ema_t0);
+    adam_update<V, EMA>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup, e, a);
 }
 
 // a <-> b in one pass (FlatAdam.swap_ema: the averaged weights change places with the raw ones, no pointer moves)
@@ -380,31 +322,25 @@ __global__ __launch_bounds__(256) void swap_kernel(float *__restrict__ a, float 
     }
 }
 
-__global__ void adam_advance_kernel(float *state, float lr, float dim_model, float warmup) {
+// The counters after an update.  guard (nullptr without `skip_nonfinite`) = [bad flag of the pending update, updates skipped,
+// skipped consecutively up to now, updates applied].  A skipped update leaves all of state alone — Adam's t, the Noam step, the
+// next rate and a pending imposed rate (state[3]) stand still.  One thread: nothing to specialise, guard is tested at run time.
+__global__ void adam_advance_kernel(float *state, float *guard, float lr, float dim_model, float warmup) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        state[0] += 1.0f;
-        state[1] += 1.0f;
-        state[2] = noam_rate(state[1], lr, dim_model, warmup);
-        state[3] = 0.f;
-    }
-}
-
-// guard = [bad flag of the pending update, updates skipped, skipped consecutively up to now, updates applied].  A skipped update
-// leaves all of state alone — Adam's t, the Noam step, the next rate and a pending imposed rate (state[3]) stand still.
-__global__ void adam_advance_guarded_kernel(float *state, float *guard, float lr, float dim_model, float warmup) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        if (guard[0] == 0.f) {
+        if (guard == nullptr || guard[0] == 0.f) {
             state[0] += 1.0f;
             state[1] += 1.0f;
             state[2] = noam_rate(state[1], lr, dim_model, warmup);
             state[3] = 0.f;
-            guard[3] += 1.0f;
-            guard[2] = 0.f;
+            if (guard != nullptr) {
+                guard[3] += 1.0f;
+                guard[2] = 0.f;
+            }
         } else {
             guard[1] += 1.0f;
             guard[2] += 1.0f;
         }
-        guard[0] = 0.f;
+        if (guard != nullptr) guard[0] = 0.f;
     }
 }
 
@@ -420,6 +356,23 @@ static inline int reduce_grid(long nv) {
     if (g > 512) g = 512;
     if (g < 1) g = 1;
     return (int)g;
+}
+
+template <bool SCALE, bool GUARD>
+static void launch_clip(float *g, long n, float scale, float clip, float *sumsq, float *guard, hipStream_t s) {
+    vec4_or_scalar(n, {g}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((clip_kernel<V, SCALE, GUARD>), dim3(reduce_grid(nv)), dim3(256), 0, s, g, nv, scale, clip, sumsq, guard);
+    });
+}
+
+template <bool GUARD, bool EMA>
+static void launch_adam(float *p, const float *g, float *m, float *v, float *e, long n, const float *state, const float *guard,
+                        float lr, float b1, float b2, float eps, float dim_model, float warmup, float ema_rate, int ema_warm,
+                        float ema_t0, hipStream_t s) {
+    vec4_or_scalar(n, {p, g, m, v, e}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((adam_kernel<V, GUARD, EMA>), dim3(stream_grid(nv)), dim3(256), 0, s, p, g, m, v, e, nv, state, guard, lr,
+                           b1, b2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
+    });
 }
 
 }  // namespace glowtts
@@ -465,11 +418,9 @@ extern "C" int glowtts_mle_fwd(const float *z, const float *m, const float *logs
     GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0, "glowtts_mle_fwd: bad shape");
     const long n = (long)B * C * T;
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(z) && aligned16(m) && aligned16(logs))
-        hipLaunchKernelGGL((mle_fwd_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, z, m, logs, mask, acc, n / 4, (long)B * T);
-    else
-        hipLaunchKernelGGL((mle_fwd_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, z, m, logs, mask, acc, n, (long)B * T);
+    vec4_or_scalar(n, {z, m, logs}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((mle_fwd_kernel<V>), dim3(reduce_grid(nv)), dim3(256), 0, (hipStream_t)stream, z, m, logs, mask, acc, nv, (long)B * T);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_mle_fwd");
 }
 
@@ -478,11 +429,9 @@ extern "C" int glowtts_mle_bwd(const float *z, const float *m, const float *logs
     GLOWTTS_CHECK_ARG(z && m && logs && scale && dz && dm && dlogs, "glowtts_mle_bwd: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0, "glowtts_mle_bwd: negative size");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(z) && aligned16(m) && aligned16(logs) && aligned16(dz) && aligned16(dm) && aligned16(dlogs))
-        hipLaunchKernelGGL((mle_bwd_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, z, m, logs, scale, dz, dm, dlogs, (long)(n / 4));
-    else
-        hipLaunchKernelGGL((mle_bwd_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, z, m, logs, scale, dz, dm, dlogs, (long)n);
+    vec4_or_scalar(n, {z, m, logs, dz, dm, dlogs}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((mle_bwd_kernel<V>), dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, z, m, logs, scale, dz, dm, dlogs, nv);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_mle_bwd");
 }
 
@@ -501,11 +450,9 @@ extern "C" int glowtts_mle_loss_bwd(const float *z, const float *m, const float 
     GLOWTTS_CHECK_ARG(z && m && logs && dloss && denom && dz && dm && dlogs && dlogdet, "glowtts_mle_loss_bwd: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0 && B >= 0, "glowtts_mle_loss_bwd: negative size");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(z) && aligned16(m) && aligned16(logs) && aligned16(dz) && aligned16(dm) && aligned16(dlogs))
-        hipLaunchKernelGGL((mle_bwd_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, z, m, logs, dloss, dz, dm, dlogs, (long)(n / 4), denom, dlogdet, B);
-    else
-        hipLaunchKernelGGL((mle_bwd_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, z, m, logs, dloss, dz, dm, dlogs, (long)n, denom, dlogdet, B);
+    vec4_or_scalar(n, {z, m, logs, dz, dm, dlogs}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((mle_bwd_kernel<V>), dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, z, m, logs, dloss, dz, dm, dlogs, nv, denom, dlogdet, B);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_mle_loss_bwd");
 }
 
@@ -534,15 +481,13 @@ extern "C" int glowtts_span_logw(const int32_t *first, const int32_t *t_x, float
     GLOWTTS_LAUNCH_CHECK("glowtts_span_logw");
 }
 
+// The optimizer tail.  Every entry point keeps its own argument checks and messages; the kernels behind them are one per pass
+// (clip_kernel, adam_kernel, adam_advance_kernel), instantiated with the entry's options.
 extern "C" int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *sumsq, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(g, "glowtts_clip_grad_value: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value: bad argument");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(g))
-        hipLaunchKernelGGL((clip_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, g, (long)(n / 4), clip, sumsq);
-    else
-        hipLaunchKernelGGL((clip_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, clip, sumsq);
+    launch_clip<false, false>(g, n, 1.0f, clip, sumsq, nullptr, (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value");
 }
 
@@ -550,12 +495,17 @@ extern "C" int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, 
     GLOWTTS_CHECK_ARG(g, "glowtts_clip_grad_value_scaled: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value_scaled: bad argument");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(g))
-        hipLaunchKernelGGL((clip_scaled_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, g, (long)(n / 4), scale, clip, sumsq);
-    else
-        hipLaunchKernelGGL((clip_scaled_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, scale, clip, sumsq);
+    launch_clip<true, false>(g, n, scale, clip, sumsq, nullptr, (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value_scaled");
+}
+
+extern "C" int glowtts_clip_grad_value_guarded(float *g, int64_t n, float scale, float clip, float *sumsq, float *guard,
+                                               glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(g && guard, "glowtts_clip_grad_value_guarded: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value_guarded: bad argument");
+    if (n == 0) return 0;
+    launch_clip<true, true>(g, n, scale, clip, sumsq, guard, (hipStream_t)stream);
+    GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value_guarded");
 }
 
 extern "C" int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state,
@@ -564,31 +514,9 @@ extern "C" int glowtts_adam_noam(float *p, const float *g, float *m, float *v, i
     GLOWTTS_CHECK_ARG(p && g && m && v && state, "glowtts_adam_noam: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam: negative size");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v))
-        hipLaunchKernelGGL((adam_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, p, g, m, v, (long)(n / 4), state, lr, beta1, beta2, eps, dim_model, warmup);
-    else
-        hipLaunchKernelGGL((adam_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, (long)n, state, lr, beta1, beta2, eps, dim_model, warmup);
+    launch_adam<false, false>(p, g, m, v, nullptr, n, state, nullptr, lr, beta1, beta2, eps, dim_model, warmup, 0.f, 0, 0.f,
+                              (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam");
-}
-
-extern "C" int glowtts_adam_advance(float *state, float lr, float dim_model, float warmup, glowtts_stream_t stream) {
-    GLOWTTS_CHECK_ARG(state, "glowtts_adam_advance: null pointer");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, lr, dim_model, warmup);
-    GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance");
-}
-
-extern "C" int glowtts_clip_grad_value_guarded(float *g, int64_t n, float scale, float clip, float *sumsq, float *guard,
-                                               glowtts_stream_t stream) {
-    GLOWTTS_CHECK_ARG(g && guard, "glowtts_clip_grad_value_guarded: null pointer");
-    GLOWTTS_CHECK_ARG(n >= 0 && clip >= 0.f, "glowtts_clip_grad_value_guarded: bad argument");
-    if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(g))
-        hipLaunchKernelGGL((clip_guarded_kernel<4>), dim3(reduce_grid(n / 4)), dim3(256), 0, s, g, (long)(n / 4), scale, clip, sumsq, guard);
-    else
-        hipLaunchKernelGGL((clip_guarded_kernel<1>), dim3(reduce_grid(n)), dim3(256), 0, s, g, (long)n, scale, clip, sumsq, guard);
-    GLOWTTS_LAUNCH_CHECK("glowtts_clip_grad_value_guarded");
 }
 
 extern "C" int glowtts_adam_noam_guarded(float *p, const float *g, float *m, float *v, int64_t n, const float *state,
@@ -597,21 +525,12 @@ extern "C" int glowtts_adam_noam_guarded(float *p, const float *g, float *m, flo
     GLOWTTS_CHECK_ARG(p && g && m && v && state && guard, "glowtts_adam_noam_guarded: null pointer");
     GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam_guarded: negative size");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v))
-        hipLaunchKernelGGL((adam_guarded_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, p, g, m, v, (long)(n / 4), state, guard, lr, beta1, beta2, eps, dim_model, warmup);
-    else
-        hipLaunchKernelGGL((adam_guarded_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, (long)n, state, guard, lr, beta1, beta2, eps, dim_model, warmup);
+    launch_adam<true, false>(p, g, m, v, nullptr, n, state, guard, lr, beta1, beta2, eps, dim_model, warmup, 0.f, 0, 0.f,
+                             (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_guarded");
 }
 
-extern "C" int glowtts_adam_advance_guarded(float *state, float *guard, float lr, float dim_model, float warmup,
-                                            glowtts_stream_t stream) {
-    GLOWTTS_CHECK_ARG(state && guard, "glowtts_adam_advance_guarded: null pointer");
-    hipLaunchKernelGGL(adam_advance_guarded_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, guard, lr, dim_model, warmup);
-    GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance_guarded");
-}
-
+// the only entry whose guard may be NULL: GUARD is chosen here, on the host
 extern "C" int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *v, float *e, int64_t n, const float *state,
                                      const float *guard, float lr, float beta1, float beta2, float eps, float dim_model,
                                      float warmup, float ema_rate, int ema_warm, float ema_t0, glowtts_stream_t stream) {
@@ -619,12 +538,23 @@ extern "C" int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *
     GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam_ema: negative size");
     GLOWTTS_CHECK_ARG(ema_rate > 0.f && ema_rate < 1.f, "glowtts_adam_noam_ema: ema_rate (1 - decay) must lie in (0, 1)");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(e))
-        hipLaunchKernelGGL((adam_ema_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, p, g, m, v, e, (long)(n / 4), state, guard, lr, beta1, beta2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
-    else
-        hipLaunchKernelGGL((adam_ema_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, p, g, m, v, e, (long)n, state, guard, lr, beta1, beta2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
+    (guard != nullptr ? launch_adam<true, true> : launch_adam<false, true>)(p, g, m, v, e, n, state, guard, lr, beta1, beta2, eps,
+                                                                           dim_model, warmup, ema_rate, ema_warm, ema_t0,
+                                                                           (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_ema");
+}
+
+extern "C" int glowtts_adam_advance(float *state, float lr, float dim_model, float warmup, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(state, "glowtts_adam_advance: null pointer");
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, (float *)nullptr, lr, dim_model, warmup);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance");
+}
+
+extern "C" int glowtts_adam_advance_guarded(float *state, float *guard, float lr, float dim_model, float warmup,
+                                            glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(state && guard, "glowtts_adam_advance_guarded: null pointer");
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, guard, lr, dim_model, warmup);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_advance_guarded");
 }
 
 extern "C" int glowtts_swap_f32(float *a, float *b, int64_t n, glowtts_stream_t stream) {
@@ -633,11 +563,9 @@ extern "C" int glowtts_swap_f32(float *a, float *b, int64_t n, glowtts_stream_t 
     const uintptr_t ua = reinterpret_cast<uintptr_t>(a), ub = reinterpret_cast<uintptr_t>(b), bytes = (uintptr_t)n * 4u;
     GLOWTTS_CHECK_ARG(ua + bytes <= ub || ub + bytes <= ua || n == 0, "glowtts_swap_f32: the buffers overlap");
     if (n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    if ((n & 3) == 0 && aligned16(a) && aligned16(b))
-        hipLaunchKernelGGL((swap_kernel<4>), dim3(stream_grid(n / 4)), dim3(256), 0, s, a, b, (long)(n / 4));
-    else
-        hipLaunchKernelGGL((swap_kernel<1>), dim3(stream_grid(n)), dim3(256), 0, s, a, b, (long)n);
+    vec4_or_scalar(n, {a, b}, [&](auto V, long nv) {
+        hipLaunchKernelGGL((swap_kernel<V>), dim3(stream_grid(nv)), dim3(256), 0, (hipStream_t)stream, a, b, nv);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_swap_f32");
 }
 

@@ -23,6 +23,19 @@ from ._hip import call, ptr, weights_state
 _ALIGN = 64  # elements: every parameter starts on a 256-byte boundary of the flat buffers
 
 
+def clip_launch(g: torch.Tensor, scale: float, clip_value: float, sumsq: torch.Tensor, guard: typing.Optional[torch.Tensor],
+                ptr: typing.Callable) -> tuple:
+    """The clip entry point for one gradient buffer and its positional arguments, `call(*clip_launch(...))`: the guarded form when the
+    owning optimizer has a `guard` (any scale), else the scaled form when `scale` != 1 (an accumulated gradient), else the plain one.
+    Nothing is launched here: FlatAdam.clip_grad_value_ and utils.clip_grad_value_ each issue through their own module's `call`
+    and hand in their own module's `ptr` (tests replace the two per module)."""
+    if guard is not None:
+        return "glowtts_clip_grad_value_guarded", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq), ptr(guard)
+    if scale != 1.0:
+        return "glowtts_clip_grad_value_scaled", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq)
+    return "glowtts_clip_grad_value", ptr(g), g.numel(), float(clip_value), ptr(sumsq)
+
+
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam arithmetic (no amsgrad / weight decay) over flat buffers, launched through the C ABI.
 
@@ -239,13 +252,7 @@ class FlatAdam(torch.optim.Optimizer):
             return None
         from .utils import _FlatGradView
         sumsq = torch.zeros(1, device=self.flat_g.device, dtype=torch.float32)
-        if self.guard is not None:
-            call("glowtts_clip_grad_value_guarded", ptr(self.flat_g), self.flat_g.numel(), float(scale), float(clip_value),
-                 ptr(sumsq), ptr(self.guard))
-        elif scale != 1.0:
-            call("glowtts_clip_grad_value_scaled", ptr(self.flat_g), self.flat_g.numel(), float(scale), float(clip_value), ptr(sumsq))
-        else:
-            call("glowtts_clip_grad_value", ptr(self.flat_g), self.flat_g.numel(), float(clip_value), ptr(sumsq))
+        call(*clip_launch(self.flat_g, scale, clip_value, sumsq, self.guard, ptr))
         return _FlatGradView(sumsq, 2.0)
 
     @torch.no_grad()
@@ -266,25 +273,16 @@ class FlatAdam(torch.optim.Optimizer):
                     p.grad = views[i]
         g = self.param_groups[0]
         b1, b2 = g["betas"]
-        if self.flat_e is not None:                   # the same update with the average carried along; the advance is the usual one
-            call("glowtts_adam_noam_ema", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v), ptr(self.flat_e),
-                 self.numel_padded, ptr(self.dev_state), ptr(self.guard), self.base_lr, float(b1), float(b2), float(g["eps"]),
-                 self.dim_model, self.warmup, self._ema_rate, int(self.ema_warmup), self._ema_t0)
-            if self.guard is not None:
-                call("glowtts_adam_advance_guarded", ptr(self.dev_state), ptr(self.guard), self.base_lr, self.dim_model, self.warmup)
-            else:
-                call("glowtts_adam_advance", ptr(self.dev_state), self.base_lr, self.dim_model, self.warmup)
-            return
-        if self.guard is not None:
-            call("glowtts_adam_noam_guarded", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
-                 self.numel_padded, ptr(self.dev_state), ptr(self.guard), self.base_lr, float(b1), float(b2), float(g["eps"]),
-                 self.dim_model, self.warmup)
-            call("glowtts_adam_advance_guarded", ptr(self.dev_state), ptr(self.guard), self.base_lr, self.dim_model, self.warmup)
-            return
-        call("glowtts_adam_noam", ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v),
-             self.numel_padded, ptr(self.dev_state), self.base_lr, float(b1), float(b2), float(g["eps"]),
-             self.dim_model, self.warmup)
-        call("glowtts_adam_advance", ptr(self.dev_state), self.base_lr, self.dim_model, self.warmup)
+        buffers = (ptr(self.flat_p), ptr(self.flat_g), ptr(self.flat_m), ptr(self.flat_v))
+        rates = (self.base_lr, float(b1), float(b2), float(g["eps"]), self.dim_model, self.warmup)
+        guarded = "_guarded" if self.guard is not None else ""
+        guard = (ptr(self.guard),) if guarded else ()
+        if self.flat_e is not None:                   # the same update with the average carried along; its guard may be NULL
+            call("glowtts_adam_noam_ema", *buffers, ptr(self.flat_e), self.numel_padded, ptr(self.dev_state), ptr(self.guard), *rates,
+                 self._ema_rate, int(self.ema_warmup), self._ema_t0)
+        else:
+            call("glowtts_adam_noam" + guarded, *buffers, self.numel_padded, ptr(self.dev_state), *guard, *rates)
+        call("glowtts_adam_advance" + guarded, ptr(self.dev_state), *guard, self.base_lr, self.dim_model, self.warmup)
 
     def state_dict(self):
         """torch.optim.Adam-compatible layout: state[i] = {step, exp_avg, exp_avg_sq} (what checkpoint.py:44 saves).  The

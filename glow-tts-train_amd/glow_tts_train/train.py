@@ -30,7 +30,7 @@ import torch
 import contextlib
 
 from . import convops
-from ._hip import call, join_side_streams, ptr, zero_scope
+from ._hip import join_side_streams, zero_scope
 from .convops import flush_groups
 from .utils import clip_grad_value_, duration_loss, mle_loss
 
@@ -157,27 +157,6 @@ def _accumulate(model, optimizer, batches, reducer=None, reuse_packs: bool = Tru
     return losses
 
 
-def _scale_clip_per_tensor(parameters, scale: float, clip_value: float) -> None:
-    """The general path of utils.clip_grad_value_ (a gradient replaced by a foreign tensor) for an accumulated gradient; with
-    the owning optimizer's `skip_nonfinite`, every launch accumulates into its guard flag."""
-    sumsq = guard = None
-    for p in parameters:
-        if p.grad is None:
-            continue
-        g = p.grad.data
-        if not g.is_contiguous():
-            g = g.contiguous()
-            p.grad.data = g
-        if sumsq is None:
-            sumsq = torch.zeros(1, device=g.device, dtype=torch.float32)
-            owner = getattr(p, "_glowtts_flat_owner", None)
-            guard = getattr(owner() if owner is not None else None, "guard", None)
-        if guard is not None:
-            call("glowtts_clip_grad_value_guarded", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq), ptr(guard))
-        else:
-            call("glowtts_clip_grad_value_scaled", ptr(g), g.numel(), float(scale), float(clip_value), ptr(sumsq))
-
-
 def train_batches(model, optimizer, batches, grad_clip: float, reducer=None, *, reuse_packs: bool = True) -> torch.Tensor:
     """ONE optimisation step from a non-empty sequence of already-resident micro-batches (they may differ in B, T_text and
     T_mel); returns the mean of their losses as a device tensor, un-synchronised.
@@ -195,10 +174,7 @@ def train_batches(model, optimizer, batches, grad_clip: float, reducer=None, *, 
     flat = getattr(optimizer, "_optim", optimizer)
     scale = 1.0 / m
     if not (hasattr(flat, "clip_grad_value_") and flat.clip_grad_value_(grad_clip, scale=scale) is not None):
-        if m == 1:
-            clip_grad_value_(model.parameters(), grad_clip)
-        else:
-            _scale_clip_per_tensor(model.parameters(), scale, grad_clip)
+        clip_grad_value_(model.parameters(), grad_clip, scale=scale)
     optimizer.step()
     return losses[0] if m == 1 else torch.stack(losses).mean()
 

@@ -76,12 +76,16 @@ class _FlatGradView:
         return f"{float(self):.6g}"
 
 
-def clip_grad_value_(parameters, clip_value, norm_type=2):
+def clip_grad_value_(parameters, clip_value, norm_type=2, scale: float = 1.0):
     """Elementwise clamp of all gradients to +-clip_value; returns the (pre-clamp) global L2 norm
     (reference utils.py:118-132).  No host synchronisation: the norm is accumulated on device and only read if the
     caller converts the return value to float (train.py:145 ignores it).  One launch per gradient buffer; with the
     flat-buffer optimizer (optimize.py) all gradients live in ONE buffer -> one launch per step.  When the optimizer that owns
-    the parameters was built with `skip_nonfinite`, both routes run the guarded kernel and leave its flag for `step()`."""
+    the parameters was built with `skip_nonfinite`, both routes run the guarded kernel and leave its flag for `step()`.
+    `scale` (not part of the reference signature) != 1: the gradients are a SUM of micro-batch gradients (train.train_batches) and
+    are multiplied by `scale` in the same pass, before the norm and the clamp."""
+    from .optimize import clip_launch          # (optimize imports this module inside a function too: neither needs the other to load)
+
     if isinstance(parameters, torch.Tensor):
         parameters = [parameters]
     params = [p for p in parameters if p.grad is not None]
@@ -98,25 +102,19 @@ def clip_grad_value_(parameters, clip_value, norm_type=2):
     # guard[0] (optimize.FlatAdam); the per-tensor launches accumulate into the one flag
     guard = getattr(owner, "guard", None)
 
-    def clip(g):
-        if guard is not None:
-            call("glowtts_clip_grad_value_guarded", ptr(g), g.numel(), 1.0, float(clip_value), ptr(sumsq), ptr(guard))
-        else:
-            call("glowtts_clip_grad_value", ptr(g), g.numel(), float(clip_value), ptr(sumsq))
-
     # one launch over the flat buffer only while EVERY .grad still is the optimizer's view of it: a hook or a wrapper that
     # replaced a .grad leaves the flat slice stale, and clamping it would skip the live gradient (the per-tensor path below)
     if flat is not None and owner is not None and all(getattr(p, "_glowtts_flat_grad", None) is flat for p in params) \
             and sum(p.numel() for p in params) == getattr(params[0], "_glowtts_flat_numel", -1) \
             and owner.flat_g is flat and owner.grads_in_place():
-        clip(flat)
+        call(*clip_launch(flat, scale, clip_value, sumsq, guard, ptr))
     else:
         for p in params:
             g = p.grad.data
             if not g.is_contiguous():
                 g = g.contiguous()
                 p.grad.data = g
-            clip(g)
+            call(*clip_launch(g, scale, clip_value, sumsq, guard, ptr))
     return _FlatGradView(sumsq, float(norm_type))
 
 

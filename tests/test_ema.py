@@ -124,6 +124,39 @@ def test_ema_update_guarded(G, adam_base, n, offset):
         assert _bits_equal(guard, before) and torch.equal(st.cpu(), st0)
 
 
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "off1"])
+@pytest.mark.parametrize("n", [5, 4100])
+def test_ema_guard_form_is_chosen_on_the_host(G, n, offset):
+    """glowtts_adam_noam_ema instantiates the update kernel with or without the guard test from `guard != NULL` alone.  n = 5 takes the
+    scalar form, n = 4100 the 16-byte one, and offset 1 forces the scalar form on it too.  Buffers of n + 8 floats, the kernel works
+    on [offset, offset + n), and every comparison is over the WHOLE buffers, the eight floats around the range included.  guard NULL
+    against a cleared guard: p, m, v, e bit-equal, and p, m, v bit-equal to glowtts_adam_noam on clones.  guard[0] = 1: p, m, v, e
+    bit-unchanged.  The kernel never writes the guard."""
+    base = [t.cuda() for t in C.adam_ema_data(n)[:5]]
+    assert all(t.numel() == n + C.PAD and t.data_ptr() % 16 == 0 for t in base)
+    case = C.EMA_CASES[3]
+    st0 = torch.tensor(C.STATE, dtype=torch.float32)
+    free = [t.clone() for t in base]
+    _ema_call(G, free, offset, n, st0.cuda(), None, case)
+    assert not _bits_equal(free[0], base[0]) and not _bits_equal(free[4], base[4])
+    held = [t.clone() for t in base]
+    guard = torch.zeros(4, device="cuda")
+    _ema_call(G, held, offset, n, st0.cuda(), guard, case)
+    plain = [t.clone() for t in base[:4]]
+    G.hip.call("glowtts_adam_noam", *(t[offset: offset + n].data_ptr() for t in plain), n, st0.cuda().data_ptr(), C.LR, C.B1, C.B2,
+               C.EPS, C.DIM, C.WARMUP)
+    for i, name in ((0, "p"), (2, "m"), (3, "v"), (4, "e")):
+        assert _bits_equal(free[i], held[i]), name
+        if i < 4:
+            assert _bits_equal(free[i], plain[i]) and _bits_equal(held[i], plain[i]), name
+    assert guard.tolist() == [0.0] * 4
+    guard[0] = 1.0
+    skipped = [t.clone() for t in base]
+    _ema_call(G, skipped, offset, n, st0.cuda(), guard, case)
+    assert all(_bits_equal(a, b) for a, b in zip(skipped, base))
+    assert guard.tolist() == [1.0, 0.0, 0.0, 0.0]
+
+
 # =============================================================================================== 3. swap
 @pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "off1"])
 @pytest.mark.parametrize("n", [1, 5, 4099, 2 ** 21 + 4])

@@ -372,8 +372,9 @@ def test_a_poisoned_micro_batch_skips_the_whole_update(G, small, poison, fp32_ma
 
 # =============================================================================================== 6. the per-tensor route
 def test_per_tensor_clip_route_sets_the_flag(G, small):
-    """One parameter's .grad replaced by a foreign tensor holding an Inf: utils.clip_grad_value_ and train._scale_clip_per_tensor
-    clamp tensor by tensor, every launch accumulating into the owner's flag; the update is skipped."""
+    """One parameter's .grad replaced by a foreign tensor holding an Inf: utils.clip_grad_value_, as train_batch calls it and as
+    train_batches does for an accumulated gradient (scale=0.5), clamps tensor by tensor, every launch accumulating into the owner's
+    flag; the update is skipped."""
     model, opt = _model(G, small, skip=True)
     flat = opt._optim
     params = list(model.parameters())
@@ -390,7 +391,7 @@ def test_per_tensor_clip_route_sets_the_flag(G, small):
             G.utils.clip_grad_value_(model.parameters(), CLIP)
             assert float(victim.grad.max()) == CLIP
         else:
-            G.train._scale_clip_per_tensor(model.parameters(), 0.5, CLIP)
+            G.utils.clip_grad_value_(model.parameters(), CLIP, scale=0.5)
             assert float(victim.grad.max()) == CLIP and float(victim.grad.min()) == 4.5
         assert float(flat.guard[0]) != 0.0
         opt.step()

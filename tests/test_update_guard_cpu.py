@@ -136,3 +136,28 @@ def test_train_refuses_before_any_launch():
     with pytest.raises(ValueError, match="GradScaler"):
         train.train_batch(None, guarded, (None,) * 5, 5.0, scaler=object())
     assert guarded.step_num == 1 and bool((guarded._optim.guard == 0).all())
+
+
+@pytest.mark.parametrize("scale", [1.0, 0.5])
+@pytest.mark.parametrize("guarded", [False, True], ids=["no guard", "guard"])
+def test_clip_launch_selects_the_entry_point_and_its_arguments(guarded, scale):
+    """optimize.clip_launch, the one place that chooses among the three clip entry points (FlatAdam.clip_grad_value_ and both routes
+    of utils.clip_grad_value_ issue what it returns): a guard gives `_guarded` at any scale, else scale != 1 gives `_scaled`, else the
+    plain entry, which takes no scale.  The tuples are written out as the call sites spelt them before the selector existed.
+    Nothing is launched and `ptr` is the caller's: CPU tensors and their addresses do here."""
+    from glow_tts_train import optimize
+
+    g, sumsq = torch.zeros(12), torch.zeros(1)
+    guard = torch.zeros(4) if guarded else None
+    got = optimize.clip_launch(g, scale, 5, sumsq, guard, lambda t: t.data_ptr())
+    if guarded:
+        want = ("glowtts_clip_grad_value_guarded", g.data_ptr(), 12, scale, 5.0, sumsq.data_ptr(), guard.data_ptr())
+    elif scale == 0.5:
+        want = ("glowtts_clip_grad_value_scaled", g.data_ptr(), 12, 0.5, 5.0, sumsq.data_ptr())
+    else:
+        want = ("glowtts_clip_grad_value", g.data_ptr(), 12, 5.0, sumsq.data_ptr())
+    assert got == want
+    assert [type(a) for a in got] == [type(a) for a in want]                  # the clip value arrives as a float, n as an int
+    from glow_tts_train import _hip
+
+    assert len(got) - 1 == len(_hip._SIGNATURES[got[0]])

@@ -326,8 +326,8 @@ extern "C" int glowtts_flow_block_fwd_io(const glowtts_flow_block *blk, const vo
     // io bit 10: W^-1 and log det W of this block are in place already (glowtts_invconv_prepare_multi: one launch for the stack)
     // io bits 11 / 12: the end conv (needs bit 9) / the start conv (needs bit 8) are the caller's as well — glowtts_flow_boundary_fwd
     // runs end conv(k), the flows between and start conv(k + 1) in one launch; this call is then the WN stack alone
-    const bool skip_head = (io & 256) != 0, skip_tail = (io & 512) != 0, w_ready = (io & 1024) != 0;
-    const bool skip_end = (io & 2048) != 0, skip_start = (io & 4096) != 0;
+    const bool skip_head = (io & GLOWTTS_FB_SKIP_HEAD) != 0, skip_tail = (io & GLOWTTS_FB_SKIP_TAIL) != 0, w_ready = (io & GLOWTTS_FB_W_READY) != 0;
+    const bool skip_end = (io & GLOWTTS_FB_SKIP_END) != 0, skip_start = (io & GLOWTTS_FB_SKIP_START) != 0;
     GLOWTTS_CHECK_ARG((!skip_end || skip_tail) && (!skip_start || skip_head), "glowtts_flow_block_fwd: io bits 11 / 12 need bits 9 / 8");
     io &= 255;
     const int io_h = io & 1, io_f = (io >> 1) & 1;
@@ -393,8 +393,8 @@ extern "C" int glowtts_flow_block_bwd_io(const glowtts_flow_block *blk, const vo
     // produced by the caller (the same fused kernel one block later in the flow): no coupling backward at the start
     // io bits 11 / 12 (glowtts_flow_boundary_bwd): dskip has been produced by the caller too (with bit 9: no end-conv backward-data
     // here) / the start conv's backward-data is the caller's (with bit 8: this call ends with the WN stack's dx_wn)
-    const bool skip_ai = (io & 256) != 0, skip_cpl = (io & 512) != 0;
-    const bool skip_end_bd = (io & 2048) != 0, skip_start_bd = (io & 4096) != 0;
+    const bool skip_ai = (io & GLOWTTS_FB_SKIP_HEAD) != 0, skip_cpl = (io & GLOWTTS_FB_SKIP_TAIL) != 0;
+    const bool skip_end_bd = (io & GLOWTTS_FB_SKIP_END) != 0, skip_start_bd = (io & GLOWTTS_FB_SKIP_START) != 0;
     GLOWTTS_CHECK_ARG((!skip_end_bd || skip_cpl) && (!skip_start_bd || skip_ai), "glowtts_flow_block_bwd: io bits 11 / 12 need bits 9 / 8");
     io &= 255;
     GLOWTTS_CHECK_ARG(!io || !two_source, "glowtts_flow_block_bwd: bf16 tensors use the d_rs form");

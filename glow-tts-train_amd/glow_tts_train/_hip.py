@@ -3,6 +3,9 @@
 PyTorch is used for device memory (``tensor.data_ptr()``) and streams (``torch.cuda.current_stream()``); the
 kernels themselves are the hand-written HIP in ``glow-tts-train_amd/csrc``.  There is NO fallback: if the library
 is missing, or a tensor handed to an operator is not a contiguous fp32 CUDA/HIP tensor, the call raises.
+
+Prototypes, structs and flag constants are read from the header at import (``_cabi.py``): a new entry point is declared
+in ``include/glowtts_hip.h`` and nowhere else.
 """
 from __future__ import annotations
 
@@ -12,173 +15,34 @@ from typing import Optional
 
 import torch
 
+from . import _cabi
+from ._cabi import HipLibraryMissing  # noqa: F401  (raised by load(), caught by importers)
+
 _PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.environ.get(
     "GLOWTTS_HIP_LIB", os.path.join(os.path.dirname(_PKG_DIR), "lib", "libglowtts_hip.so")
 )
 
-_P = ctypes.c_void_p
+# Everything below is DERIVED from the header the library is compiled against (_cabi.py): to add an entry point, declare it
+# in include/glowtts_hip.h — there is no table to extend here.
+_FUNCTIONS, _STRUCTS, CONSTANTS = _cabi.read_header()
+
+# name -> argument ctypes of every function that returns int and ends in a glowtts_stream_t (`call` appends the stream;
+# glowtts_wn_bwd's wgrad_stream is an ordinary argument)
+_SIGNATURES = {name: args[:-1] for name, (_, args, streamed) in _FUNCTIONS.items() if streamed}
+
+# HOST structs of device pointers handed to the multi-launch executors (fields and their order are the header's)
+WnLayer = _STRUCTS["glowtts_wn_layer"]
+Wrw1Problem = _STRUCTS["glowtts_wrw1_problem"]
+FlowBlock = _STRUCTS["glowtts_flow_block"]
+EncLayer = _STRUCTS["glowtts_enc_layer"]
+
+EXPORTED_SYMBOLS = sorted(_FUNCTIONS)
+
 _I = ctypes.c_int
-_L = ctypes.c_int64
-_F = ctypes.c_float
-
-# name -> argument ctypes (every function returns int; the trailing stream argument is appended automatically)
-_SIGNATURES = {
-    "glowtts_mas_path": [_P, _P, _P, _P, _I, _I, _I],
-    "glowtts_mas_path_spans": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_mas_path_from_spans": [_P, _P, _I, _I, _I],
-    "glowtts_align_logp": [_P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_align_expand_fwd": [_P, _P, _P, _I, _I, _I, _I],
-    "glowtts_align_expand_bwd": [_P, _P, _P, _I, _I, _I, _I],
-    "glowtts_mask_len": [_P, _P, _I, _I],
-    "glowtts_keep_mask": [_P, _L, _L, _F],
-    "glowtts_actnorm_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_actnorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_actnorm_stats": [_P, _P, _P, _P, _I, _I, _I],
-    "glowtts_invconv_prepare": [_P, _P, _P, _I],
-    "glowtts_invconv_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_invconv_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_actnorm_invconv_fwd": [_P] * 9 + [_I] * 4,
-    "glowtts_actnorm_invconv_bwd": [_P] * 13 + [_I] * 4,
-    "glowtts_invconv_prepare_multi": [_P, _P, _L, _I, _I],
-    "glowtts_flow_boundary_fwd": [_P] * 17 + [_I] * 6,
-    "glowtts_flow_boundary_bwd": [_P] * 15 + [_I] * 7,
-    "glowtts_flow_boundary_bwd_reduce": [_P] * 7 + [_I] * 4,
-    "glowtts_coupling_actnorm_invconv_fwd": [_P] * 11 + [_I] * 5,
-    "glowtts_coupling_actnorm_invconv_bwd": [_P] * 15 + [_I] * 5,
-    "glowtts_coupling_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I],
-    "glowtts_coupling_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_gate_fwd": [_P, _P, _P, _I, _I, _I],
-    "glowtts_gate_bwd": [_P, _P, _P, _P, _I, _I, _I],
-    "glowtts_res_skip_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_res_skip_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_conv_fwd": [_P, _L, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_conv_gate_fwd": [_P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _I],
-    "glowtts_conv_res_skip_fwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_conv_gate_bwd": [_P, _P, _P, _P, _P, _F, _P, _I, _I, _I, _I],
-    "glowtts_conv_wrw2": [_P, _L, _P, _L, _P, _L, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_conv_wrw": [_P, _L, _P, _L, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_conv_wrw_batch": [_I, _P, _L, _P, _L, _P, _L, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_conv_wrw1_multi": [_I, _P, _I, _I],
-    "glowtts_chan_layernorm_fwd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _F],
-    "glowtts_chan_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_pack_weight": [_P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_conv_split_weights": [_P, _L, _P],
-    "glowtts_wino_weights": [_P, _L, _P, _I, _P, _L],
-    "glowtts_split_planes": [_P, _L, _P, _I],
-    "glowtts_conv_wrw_planes": [_P, _L, _L, _P, _L, _L, _P, _P, _I, _I, _I, _I, _I, _I],
-    "glowtts_unpack_weight_grad": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_rowsum": [_P, _L, _P, _P, _I, _I, _I],
-    "glowtts_pack_weight_multi": [_P, _P, _I, _I],
-    "glowtts_pack_weight_planes_multi": [_P, _P, _I, _I, _P, _L, _P],
-    "glowtts_unpack_weight_grad_multi": [_P, _P, _I, _I],
-    "glowtts_gate_bwd_ts": [_P, _P, _P, _F, _P, _I, _I, _I],
-    "glowtts_rel_attn_fwd": [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_rel_attn_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_rel_attn_fwd_ex": [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_rel_attn_bwd_ex": [_P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
-    "glowtts_squeeze": [_P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_unsqueeze": [_P, _P, _P, _P, _I, _I, _I, _I],
-    "glowtts_mle_fwd": [_P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_mle_bwd": [_P, _P, _P, _P, _P, _P, _P, _L],
-    "glowtts_mle_loss_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_mle_loss_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L],
-    "glowtts_duration_loss_fwd": [_P, _P, _P, _P, _I, _L],
-    "glowtts_duration_loss_bwd": [_P, _P, _P, _P, _P, _L],
-    "glowtts_span_logw": [_P, _P, _P, _I, _I],
-    "glowtts_clip_grad_value": [_P, _L, _F, _P],
-    "glowtts_clip_grad_value_scaled": [_P, _L, _F, _F, _P],
-    "glowtts_adam_noam": [_P, _P, _P, _P, _L, _P, _F, _F, _F, _F, _F, _F],
-    "glowtts_adam_advance": [_P, _F, _F, _F],
-    # the same three behind the device-side "skip a non-finite update" flag (guard: float[4], include/glowtts_hip.h)
-    "glowtts_clip_grad_value_guarded": [_P, _L, _F, _F, _P, _P],
-    "glowtts_adam_noam_guarded": [_P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F],
-    "glowtts_adam_advance_guarded": [_P, _P, _F, _F, _F],
-    # the Adam/Noam update that also keeps an exponential moving average of the parameters (guard may be NULL), and the exchange
-    # of two flat buffers behind FlatAdam.swap_ema
-    "glowtts_adam_noam_ema": [_P, _P, _P, _P, _P, _L, _P, _P, _F, _F, _F, _F, _F, _F, _F, _I, _F],
-    "glowtts_swap_f32": [_P, _P, _L],
-    # whole WN stack per call (csrc/wn_stack.hip); the first argument is a HOST array of WnLayer
-    "glowtts_wn_fwd": [_P, _I, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _I, _I],
-    "glowtts_wn_bwd": [_P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
-    # a whole flow block per call (csrc/wn_stack.hip); the first argument is a HOST struct glowtts_flow_block
-    "glowtts_flow_block_fwd": [_P, _P, _P, _P, _P, _F] + [_P] * 9 + [_I] * 8,
-    "glowtts_flow_block_bwd": [_P, _P, _P, _P, _P, _F] + [_P] * 16 + [_I] * 9 + [_P],
-    # text-encoder neighbours in kernel epilogues and a whole transformer layer per call
-    "glowtts_conv_fwd_act": [_P, _L, _P, _P, _P, _P, _L, _P, _L] + [_I] * 11 + [_P, _F, _P, _F],
-    "glowtts_chan_layernorm_fwd_ex": [_P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _I, _F],
-    "glowtts_chan_layernorm_bwd_ex": [_P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_chan_layernorm_fwd_act": [_P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _P, _F, _I, _I, _I, _F],
-    "glowtts_chan_layernorm_bwd_act": [_P, _P, _P, _P, _F, _P, _P, _P, _P, _I, _I, _P, _F, _P, _P, _P, _P, _I, _I, _I],
-    "glowtts_embed_fwd": [_P, _P, _F, _P, _I, _I, _I, _I],
-    "glowtts_embed_bwd": [_P, _P, _F, _P, _I, _I, _I, _I],
-    "glowtts_encoder_layer_fwd": [_P] * 7 + [_F] + [_P] * 12 + [_I] * 9 + [_F],
-    "glowtts_encoder_layer_bwd": [_P] * 7 + [_F] + [_P] * 24 + [_I] * 9 + [_P],
-    # `_io` forms (bf16 activation tensors in HBM: BASELINE configs[2]); the trailing int before the stream(s) is the io flag
-    "glowtts_flow_block_fwd_io": [_P, _P, _P, _P, _P, _P, _F] + [_P] * 10 + [_I] * 9,
-    "glowtts_flow_block_bwd_io": [_P, _P, _P, _P, _P, _F] + [_P] * 18 + [_I] * 10 + [_P],
-    "glowtts_squeeze_io": [_P, _P, _P, _P, _I, _I, _I, _I, _I],
-    "glowtts_unsqueeze_io": [_P, _P, _P, _P, _I, _I, _I, _I, _I],
-    "glowtts_conv_fwd_io": [_P, _L, _P, _P, _P, _P, _L, _P, _L] + [_I] * 12,
-    "glowtts_conv_gate_fwd_io": [_P, _P, _P, _P, _P, _F, _P, _P] + [_I] * 7,
-    "glowtts_conv_res_skip_fwd_io": [_P] * 8 + [_I] * 5,
-    "glowtts_conv_gate_bwd_io": [_P, _P, _P, _P, _P, _F, _P, _P] + [_I] * 5,
-    "glowtts_res_skip_bwd_io": [_P] * 5 + [_I] * 5,
-    "glowtts_actnorm_invconv_fwd_io": [_P] * 10 + [_I] * 5,
-    "glowtts_actnorm_invconv_bwd_io": [_P] * 13 + [_I] * 5,
-    "glowtts_coupling_fwd_io": [_P, _P, _P, _P, _P] + [_I] * 6,
-    "glowtts_coupling_bwd_io": [_P] * 7 + [_I] * 6,
-    "glowtts_wn_fwd_io": [_P, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P] + [_I] * 6,
-    "glowtts_wn_bwd_io": [_P, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P] + [_I] * 10 + [_P],
-}
-
-
-class WnLayer(ctypes.Structure):
-    """struct glowtts_wn_layer (include/glowtts_hip.h): device pointers of one WN layer's packed weights and gradients."""
-    _fields_ = [(n, ctypes.c_void_p) for n in ("wf_in", "wb_in", "b_in", "wf_rs", "wb_rs", "b_rs", "dwp_in", "dwp_rs",
-                                                 "db_in", "db_rs")]
-
-
-class Wrw1Problem(ctypes.Structure):
-    """struct glowtts_wrw1_problem (include/glowtts_hip.h): one 1x1 weight gradient of a multi-problem launch."""
-    _fields_ = ([(n, ctypes.c_void_p) for n in ("x", "d", "d2", "mask_d", "mask_x", "dwp", "dbias")]
-                + [(n, ctypes.c_long) for n in ("x_bs", "d_bs", "d2_bs")]
-                + [(n, ctypes.c_int) for n in ("Cin", "M", "d_split", "reserved")])
-
-
-class FlowBlock(ctypes.Structure):
-    """struct glowtts_flow_block (include/glowtts_hip.h): one [ActNorm, InvConvNear, CouplingBlock] block's device pointers."""
-    _fields_ = ([(n, ctypes.c_void_p) for n in (
-        "logs", "bias", "w", "w_inv", "logdet_w", "wf_start", "wb_start", "b_start", "wf_end", "wb_end", "b_end",
-        "dwp_start", "dwp_end", "db_start", "db_end", "dlogs", "dbias", "dw", "layers", "pack_desc", "unpack_desc",
-        "pack_prefix", "dwp_all")]
-                + [("dwp_floats", ctypes.c_longlong), ("n_layers", ctypes.c_int), ("n_conv", ctypes.c_int),
-                   ("total_rows", ctypes.c_int), ("reserved", ctypes.c_int)])
-
-
-class EncLayer(ctypes.Structure):
-    """struct glowtts_enc_layer (include/glowtts_hip.h): one transformer layer's device pointers."""
-    _fields_ = ([(n, ctypes.c_void_p) for n in (
-        "wf_q", "wb_q", "b_q", "wf_k", "wb_k", "b_k", "wf_v", "wb_v", "b_v", "wf_o", "wb_o", "b_o",
-        "wf_1", "wb_1", "b_1", "wf_2", "wb_2", "b_2", "emb_k", "emb_v", "gamma1", "beta1", "gamma2", "beta2",
-        "dwp_q", "dwp_k", "dwp_v", "dwp_o", "dwp_1", "dwp_2", "db_q", "db_k", "db_v", "db_o", "db_1", "db_2",
-        "demb_k", "demb_v", "dgamma1", "dbeta1", "dgamma2", "dbeta2", "pack_desc", "unpack_desc", "pack_prefix", "dwp_all")]
-                + [("dwp_floats", ctypes.c_longlong), ("n_conv", ctypes.c_int), ("total_rows", ctypes.c_int),
-                   ("attn_bf16", ctypes.c_int)])
-
-
-EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["glowtts_last_error", "glowtts_abi_version", "glowtts_conv_math",
-                           "glowtts_conv_bind_planes", "glowtts_conv_bind_planes_ns", "glowtts_wn_fused",
-                           "glowtts_set_knob", "glowtts_get_knob", "glowtts_mas_spans_supported",
-                           "glowtts_conv_bind_wino", "glowtts_wino_plane_elems", "glowtts_wino_launches",
-                           "glowtts_wino_bwd_launches"])
 
 _lib: Optional[ctypes.CDLL] = None
 _fn_cache: dict = {}
-
-
-class HipLibraryMissing(RuntimeError):
-    pass
 
 
 def library_path() -> str:
@@ -196,36 +60,10 @@ def load() -> ctypes.CDLL:
             "(hipcc --offload-arch=gfx950).  This package has no CPU or eager fallback."
         )
     lib = ctypes.CDLL(_LIB_PATH)
-    lib.glowtts_last_error.restype = ctypes.c_char_p
-    lib.glowtts_last_error.argtypes = []
-    lib.glowtts_abi_version.restype = _I
-    lib.glowtts_abi_version.argtypes = []
-    lib.glowtts_conv_math.restype = _I
-    lib.glowtts_conv_math.argtypes = [_I]
-    lib.glowtts_wn_fused.restype = _I
-    lib.glowtts_wn_fused.argtypes = [_I]
-    lib.glowtts_mas_spans_supported.restype = _I
-    lib.glowtts_mas_spans_supported.argtypes = [_I, _I]
-    lib.glowtts_set_knob.restype = _I
-    lib.glowtts_set_knob.argtypes = [ctypes.c_char_p, _I]
-    lib.glowtts_get_knob.restype = _I
-    lib.glowtts_get_knob.argtypes = [ctypes.c_char_p, ctypes.POINTER(_I)]
-    lib.glowtts_conv_bind_planes.restype = _I
-    lib.glowtts_conv_bind_planes.argtypes = [_P, _L, _P]
-    lib.glowtts_conv_bind_planes_ns.restype = _I
-    lib.glowtts_conv_bind_planes_ns.argtypes = [_P, _L, _P, _I]
-    lib.glowtts_conv_bind_wino.restype = _I
-    lib.glowtts_conv_bind_wino.argtypes = [_P, _L, _P, _L]
-    lib.glowtts_wino_plane_elems.restype = _L
-    lib.glowtts_wino_plane_elems.argtypes = [_L]
-    lib.glowtts_wino_launches.restype = _L
-    lib.glowtts_wino_launches.argtypes = []
-    lib.glowtts_wino_bwd_launches.restype = _L
-    lib.glowtts_wino_bwd_launches.argtypes = []
-    for name, args in _SIGNATURES.items():
+    for name, (restype, args, _) in _FUNCTIONS.items():
         fn = getattr(lib, name)
-        fn.restype = _I
-        fn.argtypes = list(args) + [_P]
+        fn.restype = restype
+        fn.argtypes = list(args)
     _lib = lib
     _bind_fastcall(lib)
     return lib

@@ -474,6 +474,11 @@ except _hip.HipLibraryMissing:          # importable without the library (CPU-on
     pass
 
 
+# bits 8-12 of the `io` argument of glowtts_flow_block_*_io: which parts of a block its caller runs itself (include/glowtts_hip.h)
+FB_SKIP_HEAD, FB_SKIP_TAIL, FB_W_READY, FB_SKIP_END, FB_SKIP_START = (
+    _hip.CONSTANTS["GLOWTTS_FB_" + n] for n in ("SKIP_HEAD", "SKIP_TAIL", "W_READY", "SKIP_END", "SKIP_START"))
+
+
 class WNPackPlan:
     """Persistent packed-weight / packed-gradient buffers and device descriptor tables of one WN stack, so that weight
     norm + packing of all 2*n_layers convolutions is ONE launch per forward and their un-packing ONE launch per backward
@@ -1293,7 +1298,7 @@ class FlowBlockFn(Function):
                 cond_l = f32(cond.detach()).reshape(B, n_layers, 2 * H).permute(1, 0, 2).contiguous()
             call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(x_len), ptr(cond_l), ptr(drop), scale, ptr(y), ptr(y0h),
                  ptr(h0), ptr(xs), ptr(acts), ptr(ts), ptr(skip), ptr(out), ptr(z), ptr(logdet), B, C, H, T, taps, dil_rate, n_split,
-                 int(sigmoid_scale), int(io) | (1024 if w_reuse else 0))
+                 int(sigmoid_scale), int(io) | (FB_W_READY if w_reuse else 0))
         finally:
             bplan.unbind(bound)
         ctx.save_for_backward(x, m2, x_len, y, h0, acts, ts, skip, out, winv, *([] if xs is None else [xs]),
@@ -1487,9 +1492,9 @@ class FlowStackFn(Function):
                 tab.w_inv = pw + k * (n_split * n_split + 1) * 4
                 tab.logdet_w = tab.w_inv + 4 * n_split * n_split
                 tab.reserved = B if halves > 1 else 0    # utterances per layer slab when a call covers only a part of them
-                flags = int(io) | (1024 if (stack_prep or w_reuse) else 0)
+                flags = int(io) | (FB_W_READY if (stack_prep or w_reuse) else 0)
                 if halves > 1:
-                    flags |= (256 | 4096 if k > 0 else 0) | (512 | 2048 if k < nb - 1 else 0)
+                    flags |= (FB_SKIP_HEAD | FB_SKIP_START if k > 0 else 0) | (FB_SKIP_TAIL | FB_SKIP_END if k < nb - 1 else 0)
                     sig_i = int(sigmoid_scale)
                     for hh in range(halves):
                         st, hb = chains[hh], hh * Bh
@@ -1516,14 +1521,14 @@ class FlowStackFn(Function):
                          ptr(pk[0]), ptr(pk[1]), ptr(pk[2]), tab.logdet_w, pl, tab.wf_start, tab.b_start, po + (k - 1) * nC * 4,
                          py + k * nC * 4, ph + k * nH * 4, pld + (k - 1) * B * 4, pld + k * B * 4, B, C, H, T, n_split,
                          int(sigmoid_scale))
-                    flags |= 256 | 4096
+                    flags |= FB_SKIP_HEAD | FB_SKIP_START
                 elif fuse and k > 0:
                     call("glowtts_coupling_actnorm_invconv_fwd", py + (k - 1) * nC * 4, po + (k - 1) * nC * 4, pm, ptr(pk[0]), ptr(pk[1]),
                          ptr(pk[2]), tab.logdet_w, pl, py + k * nC * 4, pld + (k - 1) * B * 4, pld + k * B * 4, B, C, T, n_split,
                          int(sigmoid_scale))
-                    flags |= 256
+                    flags |= FB_SKIP_HEAD
                 if fuse and k < nb - 1:
-                    flags |= 512 | (2048 if boundary else 0)
+                    flags |= FB_SKIP_TAIL | (FB_SKIP_END if boundary else 0)
                 prev_tab = tab
                 call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), px if k == 0 else pz + (k - 1) * nC * eF, pm, pl, None,
                      None if pdr is None else pdr + k * n_layers * 2 * nH, scale, py + k * nC * eF,
@@ -1610,9 +1615,9 @@ class FlowStackFn(Function):
             tab.w_inv = pw + k * (n_split * n_split + 1) * 4
             tab.logdet_w = tab.w_inv + 4 * n_split * n_split
             fuse = ctx.fuse
-            flags = int(io) | (256 if fuse and k > 0 else 0) | (512 if fuse and k < nb - 1 else 0)
+            flags = int(io) | (FB_SKIP_HEAD if fuse and k > 0 else 0) | (FB_SKIP_TAIL if fuse and k < nb - 1 else 0)
             if boundary:
-                flags |= (4096 if k > 0 else 0) | (2048 if k < nb - 1 else 0)
+                flags |= (FB_SKIP_START if k > 0 else 0) | (FB_SKIP_END if k < nb - 1 else 0)
             bound = bplan.bind(io)
             try:
                 call("glowtts_flow_block_bwd_io", ctypes.addressof(tab), px if k == 0 else pz + (k - 1) * nC * eF, pm, pl,

@@ -599,6 +599,11 @@ int glowtts_encoder_layer_bwd(const glowtts_enc_layer *L, const float *x, const 
  *       (glowtts_coupling_actnorm_invconv_fwd / _bwd): bits 11 / 12 = the end conv (with bit 9) / the start conv (with bit 8) — in the backward their backward-data launches — are the caller's too (glowtts_flow_boundary_fwd / _bwd); bit 10 = forward: W^-1 / log det W are in place (glowtts_invconv_prepare_multi); bit 8 = forward: y has been written by the caller (no W^-1 factorisation, no
  *       ActNorm + InvConv launch) / backward: no ActNorm + InvConv backward at the end (dx is not written); bit 9 = forward: no
  *       affine apply at the end (z is not written) / backward: dy and dout have been written by the caller (no coupling backward) */
+#define GLOWTTS_FB_SKIP_HEAD  0x0100 /* bit 8 */
+#define GLOWTTS_FB_SKIP_TAIL  0x0200 /* bit 9 */
+#define GLOWTTS_FB_W_READY    0x0400 /* bit 10 */
+#define GLOWTTS_FB_SKIP_END   0x0800 /* bit 11, needs GLOWTTS_FB_SKIP_TAIL */
+#define GLOWTTS_FB_SKIP_START 0x1000 /* bit 12, needs GLOWTTS_FB_SKIP_HEAD */
 int glowtts_conv_bind_planes_ns(const float *wp, long n_floats, const uint16_t *planes, int n_planes);
 
 /* ---- Winograd F(4, 5) form of the gated in-conv (reference layers.py:146 + utils.py:31-38; csrc/convwino.hip) -------------------

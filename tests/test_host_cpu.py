@@ -37,6 +37,108 @@ def test_cabi_exports_every_declared_symbol():
     assert lib.glowtts_abi_version() == 1
 
 
+def test_cabi_reader_yields_every_prototype():
+    """The binding is derived from the header (glow_tts_train/_cabi.py): every prototype this file's own regex finds is read, the
+    ones that return int and end in a stream are `_SIGNATURES` (stream dropped), the others are typed from their prototypes too."""
+    from glow_tts_train import _cabi, _hip
+
+    text = re.sub(r"/\*.*?\*/", "", open(_cabi.HEADER_PATH).read(), flags=re.S)
+    protos = re.findall(r"\b(glowtts_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text)
+    streamed = sorted(n for n, a in protos if re.search(r"\bglowtts_stream_t\s+\w+\s*$", a))
+    functions, _, _ = _cabi.read_header()
+    assert sorted(functions) == _header_functions() == sorted(n for n, _ in protos)
+    assert sorted(_hip._SIGNATURES) == streamed and len(streamed) > len(functions) - len(streamed) > 0
+    for name, (restype, args, is_streamed) in functions.items():
+        assert is_streamed == (name in streamed)
+        if is_streamed:
+            assert restype is ctypes.c_int and args[-1] is ctypes.c_void_p and _hip._SIGNATURES[name] == args[:-1]
+    lib = _hip.load()
+    for name, (restype, args, _) in functions.items():
+        assert getattr(lib, name).restype is restype and list(getattr(lib, name).argtypes) == args, name
+    # spot checks of the type vocabulary against prototypes read by eye
+    assert functions["glowtts_last_error"] == (ctypes.c_char_p, [], False)
+    assert functions["glowtts_set_knob"] == (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int], False)
+    assert functions["glowtts_wino_plane_elems"] == (ctypes.c_int64, [ctypes.c_int64], False)
+    assert _hip._SIGNATURES["glowtts_keep_mask"] == [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_float]
+    assert _hip._SIGNATURES["glowtts_wn_bwd"][-1] is ctypes.c_void_p          # wgrad_stream stays in the row
+
+
+def test_cabi_struct_layouts_match_the_c_compiler(tmp_path):
+    """sizeof / offsetof of every struct of the header as gcc lays it out, against the ctypes classes derived from it."""
+    import subprocess
+
+    from glow_tts_train import _cabi, _hip
+
+    structs = {"glowtts_wn_layer": _hip.WnLayer, "glowtts_wrw1_problem": _hip.Wrw1Problem, "glowtts_flow_block": _hip.FlowBlock,
+               "glowtts_enc_layer": _hip.EncLayer}
+    assert sorted(structs) == sorted(re.findall(r"typedef\s+struct\s+(\w+)", open(_cabi.HEADER_PATH).read()))
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "glowtts_hip.h"', 'int main(void) {']
+    for name, cls in structs.items():
+        lines.append(f'    printf("{name} - %zu 0\\n", sizeof({name}));')
+        for field, _ in cls._fields_:
+            lines.append(f'    printf("{name} {field} %zu %zu\\n", sizeof((({name} *)0)->{field}), offsetof({name}, {field}));')
+    lines += ['    return 0;', '}']
+    (tmp_path / "layout.c").write_text("\n".join(lines) + "\n")
+    subprocess.run(["gcc", "-I", os.path.dirname(_cabi.HEADER_PATH), str(tmp_path / "layout.c"), "-o", str(tmp_path / "layout")],
+                   check=True)
+    got = subprocess.run([str(tmp_path / "layout")], check=True, capture_output=True, text=True).stdout.split("\n")
+    want = []
+    for name, cls in structs.items():
+        want.append(f"{name} - {ctypes.sizeof(cls)} 0")
+        want += [f"{name} {field} {getattr(cls, field).size} {getattr(cls, field).offset}" for field, _ in cls._fields_]
+    assert got == want + [""]
+    assert len(_hip.EncLayer._fields_) == 50 and [f for f, _ in _hip.WnLayer._fields_][:4] == ["wf_in", "wb_in", "b_in", "wf_rs"]
+
+
+def test_cabi_reader_refuses_what_it_does_not_understand():
+    from glow_tts_train import _cabi
+
+    P, I, L, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float
+    functions, structs, constants = _cabi.parse("""
+        /* a comment with a prototype in it: int glowtts_not_this(double x); */
+        #include <stdint.h>
+        #define GLOWTTS_SOME_FLAG 0x0100   /* bit 8 */
+        #define GLOWTTS_OTHER 7
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        typedef void *glowtts_stream_t;
+        typedef struct glowtts_thing {
+            const float *a, *b;     /* two pointers on one line */
+            long n; long long m;
+            int p, q, r;
+            float s;
+        } glowtts_thing;
+        int glowtts_split(const glowtts_thing *t, const float *const *x,
+                          unsigned long long seed, int64_t n,
+                          float f,
+                          glowtts_stream_t side, glowtts_stream_t stream);
+        long glowtts_count(void);
+        const char *glowtts_text(const char *name, int *out);
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    assert functions == {"glowtts_split": (I, [P, P, L, L, F, P, P], True), "glowtts_count": (L, [], False),
+                         "glowtts_text": (ctypes.c_char_p, [ctypes.c_char_p, P], False)}
+    assert constants == {"GLOWTTS_SOME_FLAG": 256, "GLOWTTS_OTHER": 7}
+    assert [(n, t) for n, t in structs["glowtts_thing"]._fields_] == [
+        ("a", P), ("b", P), ("n", L), ("m", L), ("p", I), ("q", I), ("r", I), ("s", F)]
+    for bad in ("int glowtts_bad(const float *x, double y, glowtts_stream_t stream);",
+                "typedef struct glowtts_v { int n; } glowtts_v;\nint glowtts_bad(glowtts_v by_value, glowtts_stream_t stream);",
+                "double glowtts_bad(int n);",
+                "int glowtts_bad(int n, unsigned k);",
+                "int glowtts_bad(int);"):
+        with pytest.raises(ValueError, match="glowtts_bad"):
+            _cabi.parse("typedef void *glowtts_stream_t;\n" + bad)
+    with pytest.raises(ValueError, match="glowtts_v"):
+        _cabi.parse("typedef struct glowtts_v { double d; } glowtts_v;")
+    with pytest.raises(ValueError, match="glowtts_v"):
+        _cabi.parse("typedef struct glowtts_v { int n[4]; } glowtts_v;")
+    with pytest.raises(_cabi.HipLibraryMissing, match="no_such_header.h"):
+        _cabi.read_header("/nonexistent/no_such_header.h")
+
+
 def test_cabi_argument_errors_do_not_need_a_gpu():
     """Argument validation happens on the host before any launch: exercise it without a device."""
     from glow_tts_train import _hip

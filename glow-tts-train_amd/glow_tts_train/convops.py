@@ -8,6 +8,8 @@ already exists (the flat-buffer optimizer keeps it allocated), which removes one
 """
 from __future__ import annotations
 
+import ctypes
+import functools
 import os
 from typing import List, Optional
 
@@ -1129,7 +1131,6 @@ class FlowBlockPlan:
         return [sv, sg, sb, ev, None, eb] + list(params[8: 8 + 6 * n_layers])
 
     def table(self, params, n_layers):
-        import ctypes
         plan = self.plan
         convp = self.conv_params(params, n_layers)
         key = (plan.version, tuple(0 if p is None else p.data_ptr() for p in params),
@@ -1243,6 +1244,149 @@ def flow_block_params(actnorm, invconv, coupling):
     return out
 
 
+class FlowSlabs:
+    """Where block k's part of every slab of the flow decoder lives: the ONE statement of the slab layout, for the forward
+    and the backward of FlowBlockFn (nb = 1 over its own tensors) and of FlowStackFn (the (nb, ...) slabs).  Plain integers:
+    base pointers in, pointers out, built once per node call; `block()` is integer arithmetic only.
+        flow tensors  x (B, C, T) | z, y (nb, B, C, T) in the flow dtype (bf16 with io & 2) | out (nb, B, C, T) fp32
+        hidden        h0, skip (nb, B, H, T) | acts (nb, n_layers, B, H, T) | ts (nb, n_layers, B, 2H, T)
+                      | xs (nb, max(n_layers - 1, 1), B, H, T) | y0h (nb, B, C / 2, T), in the hidden dtype (bf16 with io & 1)
+        masks         m2 (B, T) fp32 | x_len (B) int32 | drop (nb, n_layers, B, 2H, T) bytes
+        per block     logdet (nb, B) fp32 | w_inv (nb, n_split^2 + 1) fp32: W^-1, then log det W
+        gradients     dz (B, C, T), dy, dx (nb, B, C, T) flow dtype | dlogdet (B) fp32 | dout (nb, B, C, T), dskip (nb, B, H, T),
+                      d_xin (nb, n_layers, B, 2H, T), dx_wn (nb, n_layers, B, H, T) hidden dtype
+                      | d_rs (nb, B, H, T) with the two-source launch sequence, else (nb, n_layers, B, 2H, T)
+    A slab that a run does not have is None, and so is every pointer into it."""
+
+    LEAD_Y, LEAD_H0, LEAD_SKIP, LEAD_OUT = 5, 7, 11, 12           # places in block()'s thirteen leading arguments
+    __slots__ = ("dims", "ptrs", "two_src", "grad_ptrs")
+
+    def __init__(self, nb, n_layers, B, C, H, T, io, n_split, scale, ptrs, two_src=False, grad_ptrs=None):
+        # ptrs: x, m2, x_len, drop, y, y0h, h0, xs, acts, ts, skip, out, z, logdet, w_inv; grad_ptrs (the backward, and `block()` then
+        # also returns block k's nine gradient arguments): dz, dlogdet, dy, dout, dskip, d_rs, d_xin, dx_wn, dx.
+        # Two tuples, unpacked into locals by block() (the host is close to being the step's bottleneck: profiles/slab_fold_bench.txt);
+        # dims holds, after T, the bytes per element and the elements of one utterance of a flow / of a hidden tensor.
+        self.dims = (nb, n_layers, B, T, 2 if io & 2 else 4, 2 if io & 1 else 4, C * T, H * T, n_split * n_split, scale)
+        self.ptrs, self.two_src, self.grad_ptrs = ptrs, two_src, grad_ptrs
+
+    def block(self, k, first_utt=0, n_utt=None):
+        """(lead, z, logdet, w_inv, logdet_w, grads) of block k for the utterances first_utt .. first_utt + n_utt of the batch:
+        lead  = x_in, m2, x_len, drop, scale, y, y0h, h0, xs, acts, ts, skip, out — the leading arguments that
+                glowtts_flow_block_fwd_io (which takes its cond rows after x_len) and _bwd_io share; x_in is x or z of block k - 1;
+        grads = dz_in, dlogdet, dy, dout, dskip, d_rs, d_xin, dx_wn, dx (dz_in is dz or dx of block k + 1), None in the forward."""
+        nb, nl, B, T, eF, eA, uC, uH, nn, scale = self.dims
+        x, m2, x_len, drop, y, y0h, h0, xs, acts, ts, skip, out, z, logdet, w_inv = self.ptrs
+        u = first_utt
+        if k < 0 or k >= nb or u < 0 or u + (B if n_utt is None else n_utt) > B:
+            raise ValueError(f"FlowSlabs.block({k}, {first_utt}, {n_utt}): outside {nb} blocks of {B} utterances")
+        bu, lu = k * B + u, k * nl * B + u                  # utterance index in a (nb, B, ...) / (nb, n_layers, B, ...) slab
+        cF, hA, lA = bu * uC * eF, bu * uH * eA, lu * uH * eA
+        lead = (x + u * uC * eF if k == 0 else z + cF - B * uC * eF, m2 + u * T * 4, x_len + u * 4,
+                None if drop is None else drop + lu * 2 * uH, scale, y + cF, None if y0h is None else y0h + bu * (uC // 2) * eA,
+                h0 + hA, None if xs is None or nl == 1 else xs + (k * (nl - 1) * B + u) * uH * eA,     # (one layer: no x_{l+1} is kept)
+                acts + lA, ts + 2 * lA, skip + hA, out + bu * uC * 4)
+        w_inv += k * (nn + 1) * 4
+        g = self.grad_ptrs
+        if g is not None:
+            dz, dlogdet, dy, dout, dskip, d_rs, d_xin, dx_wn, dx = g
+            g = (dz + u * uC * eF if k == nb - 1 else dx + cF + B * uC * eF, dlogdet + u * 4, dy + cF, dout + bu * uC * eA,
+                 dskip + hA, d_rs + (hA if self.two_src else 2 * lA), d_xin + 2 * lA, dx_wn + lA, dx + cF)
+        # (FlowBlockFn keeps no z for its backward, nobody the log-determinants)
+        return (lead, None if z is None else z + cF, None if logdet is None else logdet + bu * 4, w_inv, w_inv + 4 * nn, g)
+
+
+# ---- what the two flow nodes share ------------------------------------------------------------------------------------------
+def _flow_dtypes(io):
+    """(flow tensor dtype, hidden tensor dtype) of the `_io` entry points (csrc): io 0 = fp32 tensors; 1 = the coupling
+    network's hidden tensors bf16 in HBM, the flow tensor fp32; 3 = the flow tensor bf16 as well."""
+    return (torch.bfloat16 if io & 2 else torch.float32), (torch.bfloat16 if io & 1 else torch.float32)
+
+
+def _flow_input(who, x, io):
+    """(the flow tensor, dense; its dtype; the hidden tensors' dtype)"""
+    fdt, adt = _flow_dtypes(io)
+    if x.dtype != fdt:
+        raise RuntimeError(f"{who}: flow tensor is {x.dtype}, it runs with {fdt} flow tensors")
+    return x.contiguous(), fdt, adt
+
+
+def _flow_keep_mask(drop, p_drop, shape, dev, site):
+    """The WN stacks' dropout keep-mask: the caller's when it has the shape the launch sequence reads, else drawn here."""
+    if p_drop <= 0.0:
+        return None
+    if drop is None or tuple(drop.shape) != shape or not drop.is_contiguous():
+        drop = ops.keep_mask(shape, p_drop, dev, site)
+    return drop
+
+
+def _winv_slab(bplan, winv, n_split, weights):
+    """(slab of W^-1 / log det W to use, True if it is filled already).  An accumulated update (weights_unchanged): what the
+    update's first micro-batch made, kept on `bplan` under the weights' addresses."""
+    if not (_WS.active or _WS.record):
+        return winv, False
+    wk = (_WS.epoch, n_split, *weights)
+    cached = getattr(bplan, "_winv_cache", None)
+    if _WS.active and cached is not None and cached[0] == wk:
+        return cached[1], True
+    bplan._winv_cache = (wk, winv)
+    return winv, False
+
+
+def _save_tensors(ctx, *tensors):
+    """save_for_backward of the tensors that are there; `_saved_tensors` hands them back with None in the others' places."""
+    ctx.saved_missing = missing = [i for i, t in enumerate(tensors) if t is None]
+    ctx.save_for_backward(*([t for t in tensors if t is not None] if missing else tensors))
+
+
+def _saved_tensors(ctx):
+    saved = list(ctx.saved_tensors)
+    for i in ctx.saved_missing:
+        saved.insert(i, None)
+    return saved
+
+
+def _check_grad_buffers(who, params):
+    if not all(p.grad is not None and p.grad.is_contiguous() for p in params):
+        raise RuntimeError(f"{who}: a parameter gradient buffer disappeared between forward and backward")
+
+
+def _flow_grad_inputs(dz, dlogdet, x, io):
+    fdt = _flow_dtypes(io)[0]
+    dz = dz.contiguous() if dz is not None else torch.zeros_like(x)
+    if dz.dtype != fdt:
+        dz = dz.to(fdt)
+    dlogdet = dlogdet.contiguous().float() if dlogdet is not None else torch.zeros(x.shape[0], device=x.device)
+    return dz, dlogdet
+
+
+def _two_src(io, dil_rate, H, T):
+    # the two-source launch sequence (d_rs never materialised, batched weight gradients) also where the weight gradients stay
+    # on the chain's stream — the backward's last block, and every block of a one-stream run (rocprofv3 passes then time the
+    # launches the step really makes): 14.83 -> 14.75 ms per step (tools/ab_flags.py, four alternating pairs)
+    return (not io) and dil_rate == 1 and H % 192 == 0 and T % 4 == 0
+
+
+def _record_for_wgrad(stream, *tensors):
+    """`tensors` are read by launches on `stream` that may run after the node that owns them has returned — the MASKS included: the
+    start conv's weight gradient multiplies its d operand by the mask (the only 1x1 weight gradient that does).  It is a small
+    tensor made in the forward, freed when the last block's backward returns — and the caching allocator then hands its memory to the
+    next small allocation on the main stream while the side stream, a block or two behind, has not run that launch yet: the start
+    conv of the last side-stream block(s) came out with a weight AND bias gradient of zero, once in ~200 steps in native-fp32
+    arithmetic (where the side stream lags most), 3 of ~25 full test-suite runs (round 5; tools/race_hunt_c5.py)"""
+    for t in tensors:
+        if t is not None:
+            t.record_stream(stream)
+
+
+def _notify_on(side, live):
+    """Every gradient of `live` is complete at this point of the stream `side` (None: of the current stream)."""
+    if side is None:
+        _notify(live)
+    else:
+        with torch.cuda.stream(side):
+            _notify(live)
+
+
 class FlowBlockFn(Function):
     """One decoder block — ActNorm, InvConvNear, CouplingBlock (reference models.py:176-190; layers.py:182-199, 238-272;
     attentions.py:119-142) — as ONE autograd node whose forward and backward are one native call each
@@ -1251,15 +1395,8 @@ class FlowBlockFn(Function):
     @staticmethod
     def forward(ctx, x, m2, x_len, drop, cfg, bplan, cond, *params):
         # cond: None or the speaker conditioning rows (B, 2H * n_layers, 1) = wn.cond_layer(g) (reference layers.py:142-150)
-        import ctypes
         n_split, sigmoid_scale, p_drop, dil_rate, n_layers, H, io = cfg[:7]
-        # io (csrc: the `_io` entry points): 0 = fp32 tensors; 1 = the coupling network's hidden tensors bf16 in HBM, the
-        # flow tensor fp32; 3 = the flow tensor bf16 as well
-        fdt = torch.bfloat16 if io & 2 else torch.float32
-        adt = torch.bfloat16 if io & 1 else torch.float32
-        x = x.contiguous()
-        if x.dtype != fdt:
-            raise RuntimeError(f"FlowBlockFn: flow tensor is {x.dtype}, the block runs with {fdt} flow tensors")
+        x, fdt, adt = _flow_input("FlowBlockFn", x, io)
         B, C, T = x.shape
         dev = x.device
         plan = bplan.plan
@@ -1276,33 +1413,24 @@ class FlowBlockFn(Function):
             acts, ts = act(n_layers, B, H, T), act(n_layers, B, 2 * H, T)
             xs = act(n_layers - 1, B, H, T) if n_layers > 1 else None
             logdet = new(B)
-            winv = new(n_split * n_split + 1)
-            w_reuse = False                              # (an accumulated update: W^-1 / log det W of the update's first micro-batch)
-            if _WS.active or _WS.record:
-                wk = (_WS.epoch, n_split, params[2].data_ptr())
-                cached = getattr(bplan, "_winv_cache", None)
-                if _WS.active and cached is not None and cached[0] == wk:
-                    winv, w_reuse = cached[1], True
-                else:
-                    bplan._winv_cache = (wk, winv)
-            if p_drop > 0.0 and (drop is None or tuple(drop.shape) != (n_layers, B, 2 * H, T) or not drop.is_contiguous()):
-                drop = ops.keep_mask((n_layers, B, 2 * H, T), p_drop, dev, f"decoder.block.{cfg[7] if len(cfg) > 7 else 0}")
-            if p_drop <= 0.0:
-                drop = None
-            tab = bplan.table(params, n_layers)
-            tab.w_inv, tab.logdet_w = winv.data_ptr(), winv.data_ptr() + 4 * n_split * n_split
+            # (an accumulated update: W^-1 / log det W of the update's first micro-batch)
+            winv, w_reuse = _winv_slab(bplan, new(n_split * n_split + 1), n_split, (params[2].data_ptr(),))
+            drop = _flow_keep_mask(drop, p_drop, (n_layers, B, 2 * H, T), dev, f"decoder.block.{cfg[7] if len(cfg) > 7 else 0}")
             taps = params[8].shape[2]
             scale = 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0
+            slabs = FlowSlabs(1, n_layers, B, C, H, T, io, n_split, scale,
+                              [ptr(t) for t in (x, m2, x_len, drop, y, y0h, h0, xs, acts, ts, skip, out, z, logdet, winv)])
+            lead, pz, pld, w_inv, logdet_w, _ = slabs.block(0)
+            tab = bplan.table(params, n_layers)
+            tab.w_inv, tab.logdet_w = w_inv, logdet_w
             cond_l = None
             if cond is not None:                         # layer-major rows (n_layers, B, 2H) for the gate kernels
                 cond_l = f32(cond.detach()).reshape(B, n_layers, 2 * H).permute(1, 0, 2).contiguous()
-            call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(x_len), ptr(cond_l), ptr(drop), scale, ptr(y), ptr(y0h),
-                 ptr(h0), ptr(xs), ptr(acts), ptr(ts), ptr(skip), ptr(out), ptr(z), ptr(logdet), B, C, H, T, taps, dil_rate, n_split,
-                 int(sigmoid_scale), int(io) | (FB_W_READY if w_reuse else 0))
+            call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), *lead[:3], ptr(cond_l), *lead[3:], pz, pld, B, C, H, T, taps,
+                 dil_rate, n_split, int(sigmoid_scale), int(io) | (FB_W_READY if w_reuse else 0))
         finally:
             bplan.unbind(bound)
-        ctx.save_for_backward(x, m2, x_len, y, h0, acts, ts, skip, out, winv, *([] if xs is None else [xs]),
-                              *([] if drop is None else [drop]), *([] if y0h is None else [y0h]))
+        _save_tensors(ctx, x, m2, x_len, y, h0, acts, ts, skip, out, winv, xs, drop, y0h)
         ctx.cfg, ctx.bplan, ctx.params, ctx.taps, ctx.scale = cfg, bplan, params, taps, scale
         ctx.cond_shape = None if cond is None else tuple(cond.shape)
         return z, logdet
@@ -1310,93 +1438,71 @@ class FlowBlockFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, dlogdet):
-        import ctypes
         n_split, sigmoid_scale, p_drop, dil_rate, n_layers, H, io = ctx.cfg[:7]
         block_index = ctx.cfg[7] if len(ctx.cfg) > 7 else 1 << 30
-        fdt = torch.bfloat16 if io & 2 else torch.float32
-        adt = torch.bfloat16 if io & 1 else torch.float32
-        sv = list(ctx.saved_tensors)
-        x, m2, x_len, y, h0, acts, ts, skip, out, winv = sv[:10]
-        rest = sv[10:]
-        xs = rest.pop(0) if n_layers > 1 else None
-        drop = rest.pop(0) if p_drop > 0 else None
-        y0h = rest.pop(0) if io == 1 else None
+        fdt, adt = _flow_dtypes(io)
+        x, m2, x_len, y, h0, acts, ts, skip, out, winv, xs, drop, y0h = _saved_tensors(ctx)
         params, bplan = ctx.params, ctx.bplan
-        plan = bplan.plan
         B, C, T = x.shape
         dev = x.device
-        if not all(p.grad is not None and p.grad.is_contiguous() for p in params):
-            raise RuntimeError("FlowBlockFn.backward: a parameter gradient buffer disappeared between forward and backward")
+        _check_grad_buffers("FlowBlockFn.backward", params)
         new = lambda *shape: torch.empty(shape, device=dev, dtype=adt)                                    # noqa: E731
         flow = lambda *shape: torch.empty(shape, device=dev, dtype=fdt)                                   # noqa: E731
-        dz = dz.contiguous() if dz is not None else torch.zeros_like(x)
-        if dz.dtype != fdt:
-            dz = dz.to(fdt)
-        dlogdet = dlogdet.contiguous().float() if dlogdet is not None else torch.zeros(B, device=dev)
+        dz, dlogdet = _flow_grad_inputs(dz, dlogdet, x, io)
         wgrad = _WgradStream(dev)
         if block_index < _WGRAD_MAIN_BLOCKS:
             wgrad.enabled = False                    # the backward's last blocks: their weight gradients stay on the chain's stream
-        # the two-source launch sequence (d_rs never materialised, batched weight gradients) also where the weight gradients stay
-        # on the chain's stream — the backward's last block, and every block of a one-stream run (rocprofv3 passes then time the
-        # launches the step really makes): 14.83 -> 14.75 ms per step (tools/ab_flags.py, four alternating pairs)
-        two_src = (not io) and dil_rate == 1 and H % 192 == 0 and T % 4 == 0
+        two_src = _two_src(io, dil_rate, H, T)
         dy, dout, dx = flow(B, C, T), new(B, C, T), flow(B, C, T)
         dskip = new(B, H, T)
         d_rs = new(B, H, T) if two_src else new(n_layers, B, 2 * H, T)
         d_xin, dx_wn = new(n_layers, B, 2 * H, T), new(n_layers, B, H, T)
+        slabs = FlowSlabs(1, n_layers, B, C, H, T, io, n_split, ctx.scale,
+                          [ptr(t) for t in (x, m2, x_len, drop, y, y0h, h0, xs, acts, ts, skip, out)] + [None, None, ptr(winv)],
+                          two_src, [ptr(t) for t in (dz, dlogdet, dy, dout, dskip, d_rs, d_xin, dx_wn, dx)])
         tab = bplan.table(params, n_layers)
-        tab.w_inv, tab.logdet_w = winv.data_ptr(), winv.data_ptr() + 4 * n_split * n_split
         dcond_l = None
         if ctx.cond_shape is not None:
             dcond_l = scratch_zeros((n_layers, B, 2 * H), dev)
         bound = bplan.bind(io)
         try:
-            call("glowtts_flow_block_bwd_io", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(x_len), ptr(drop), ctx.scale, ptr(y),
-                 ptr(y0h), ptr(h0), ptr(xs), ptr(acts), ptr(ts), ptr(skip), ptr(out), ptr(dz), ptr(dlogdet), ptr(dy), ptr(dout), ptr(dskip),
-                 ptr(d_rs), ptr(d_xin), ptr(dx_wn), ptr(dx), ptr(dcond_l), B, C, H, T, ctx.taps, dil_rate, n_split, int(sigmoid_scale),
-                 int(two_src), int(io), wgrad.side.cuda_stream if wgrad.enabled else None)
+            lead, _, _, tab.w_inv, tab.logdet_w, grads = slabs.block(0)
+            call("glowtts_flow_block_bwd_io", ctypes.addressof(tab), *lead, *grads, ptr(dcond_l), B, C, H, T, ctx.taps, dil_rate,
+                 n_split, int(sigmoid_scale), int(two_src), int(io), wgrad.side.cuda_stream if wgrad.enabled else None)
         finally:
             bplan.unbind(bound)
         live = [p for p in params if p is not None]
         _mark_direct(live, True)
         if wgrad.enabled:
-            # ... the MASK included: the start conv's weight gradient multiplies its d operand by it (the only 1x1 weight gradient that
-            # does).  It is a small tensor made in the forward, freed when the last block's backward returns — and the caching allocator
-            # then hands its memory to the next small allocation on the main stream while the side stream, a block or two behind, has
-            # not run that launch yet: the start conv of the last side-stream block(s) came out with a weight AND bias gradient of
-            # zero, once in ~200 steps in native-fp32 arithmetic (where the side stream lags most), 3 of ~25 full test-suite runs
-            # (round 5; tools/race_hunt_c5.py)
-            for t in (y, y0h, h0, xs, acts, skip, dout, dskip, d_rs, d_xin, dx_wn, m2):     # read by the second stream after this returns
-                if t is not None:
-                    t.record_stream(wgrad.side)
-            with torch.cuda.stream(wgrad.side):          # every gradient of the block is complete at this point of THAT stream
-                _notify(live)
-        else:
-            _notify(live)
+            _record_for_wgrad(wgrad.side, y, y0h, h0, xs, acts, skip, dout, dskip, d_rs, d_xin, dx_wn, m2)
+        _notify_on(wgrad.side if wgrad.enabled else None, live)
         dcond = None if dcond_l is None else dcond_l.permute(1, 0, 2).reshape(ctx.cond_shape)
         return (dx, None, None, None, None, None, dcond) + (None,) * len(params)
+
+
+def _split_params(params, counts):
+    """The stack nodes' flat parameter list as one tuple per block / layer."""
+    out, o = [], 0
+    for c in counts:
+        out.append(params[o: o + c])
+        o += c
+    return out
 
 
 class FlowStackFn(Function):
     """ALL decoder blocks of FlowSpecDecoder (reference models.py:193-211: the loop over `self.flows`) as ONE autograd node
     (round 4).  The launch sequence is FlowBlockFn's, block by block — one `glowtts_flow_block_fwd_io` /
     `_bwd_io` call each — but the host does per STACK what it did per block: one allocation per kind of activation slab
-    ((n_blocks, ...) tensors; a block's buffers are slices addressed by pointer arithmetic), one saved-tensor list, one autograd
+    ((n_blocks, ...) tensors; a block's buffers are slices addressed through FlowSlabs), one saved-tensor list, one autograd
     node instead of twelve.  Per block the Python side is the weight pack, the plane binding, the cached table and one C call.
     fp32 or bf16 tensors (`io` as in FlowBlockFn), no conditioning input; anything else takes the per-block nodes."""
 
     @staticmethod
     def forward(ctx, x, m2, x_len, drops, cfg, bplans, counts, *params):
-        import ctypes
         params, ctx.n_param_args = _unpack_params(params)
         n_split, sigmoid_scale, p_drop, dil_rate, n_layers, H, io = cfg
-        fdt = torch.bfloat16 if io & 2 else torch.float32
-        adt = torch.bfloat16 if io & 1 else torch.float32
-        eF, eA = (2 if io & 2 else 4), (2 if io & 1 else 4)
         nb = len(bplans)
-        x = x.contiguous()
-        if x.dtype != fdt:
-            raise RuntimeError(f"FlowStackFn: flow tensor is {x.dtype}, the stack runs with {fdt} flow tensors")
+        x, fdt, adt = _flow_input("FlowStackFn", x, io)
         B, C, T = x.shape
         dev = x.device
         new = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)                      # noqa: E731
@@ -1406,82 +1512,55 @@ class FlowStackFn(Function):
         y0h = act(nb, B, C // 2, T) if io == 1 else None
         h0, skip = act(nb, B, H, T), act(nb, B, H, T)
         acts, ts = act(nb, n_layers, B, H, T), act(nb, n_layers, B, 2 * H, T)
-        nx = max(n_layers - 1, 1)
-        xs = act(nb, nx, B, H, T)
+        xs = act(nb, max(n_layers - 1, 1), B, H, T)
         logdets = new(nb, B)
         winv = new(nb, n_split * n_split + 1)
-        if p_drop > 0.0 and (drops is None or tuple(drops.shape) != (nb, n_layers, B, 2 * H, T) or not drops.is_contiguous()):
-            drops = ops.keep_mask((nb, n_layers, B, 2 * H, T), p_drop, dev, "decoder.wn")
-        if p_drop <= 0.0:
-            drops = None
+        drops = _flow_keep_mask(drops, p_drop, (nb, n_layers, B, 2 * H, T), dev, "decoder.wn")
         scale = 1.0 / (1.0 - p_drop) if p_drop > 0 else 1.0
-        nC, nH = B * C * T, B * H * T                             # elements of a flow / hidden tensor
-        px, pm, pl = ptr(x), ptr(m2), ptr(x_len)
-        pz, py, po, ph, psk, py0 = ptr(zs), ptr(y), ptr(out), ptr(h0), ptr(skip), ptr(y0h)
-        pa, pts, pxs, pld, pw = ptr(acts), ptr(ts), ptr(xs), ptr(logdets), ptr(winv)
-        pdr = ptr(drops)
         taps = params[8].shape[2]
+        pks = _split_params(params, counts)
+        w_ptrs = [pk[2].data_ptr() for pk in pks]                 # every block's invertible 1x1 convolution weight
         # an accumulated update (weights_unchanged): W^-1 / log det W of every block as the update's first micro-batch made them
-        w_reuse = False
-        if _WS.active or _WS.record:
-            o2, wk = 0, [_WS.epoch, n_split]
-            for k in range(nb):
-                wk.append(params[o2 + 2].data_ptr())
-                o2 += counts[k]
-            cached = getattr(bplans[0], "_winv_cache", None)
-            if _WS.active and cached is not None and cached[0] == wk:
-                winv, w_reuse = cached[1], True
-                pw = ptr(winv)
-            else:
-                bplans[0]._winv_cache = (wk, winv)
+        winv, w_reuse = _winv_slab(bplans[0], winv, n_split, w_ptrs)
+        slabs = FlowSlabs(nb, n_layers, B, C, H, T, io, n_split, scale,
+                          [ptr(t) for t in (x, m2, x_len, drops, y, y0h, h0, xs, acts, ts, skip, out, zs, logdets, winv)])
         # fp32 tensors: block k's affine apply runs fused with block k + 1's ActNorm + InvConv (one pass over the flow tensor
         # instead of two; z_k is never written) — the block executors are told to leave those launches out (io bits 8 / 9)
         fuse = _FUSE_FLOWS and io == 0 and nb > 1 and n_split in (2, 4)      # (the fused kernels keep a group in registers: N <= 4)
         # ... and, where the shapes allow, end conv(k) + those flows + start conv(k + 1) as ONE launch (csrc/flow_boundary.hip)
         boundary = fuse and _FLOW_BOUNDARY and T % 4 == 0 and C <= 192 and C // n_split <= 64 and H <= 192
-        prev_tab = None
         stack_pack = _STACK_PACK and nb > 1
         if stack_pack:                                            # every block's weight norm + packing (+ planes) in ONE launch
             st = getattr(bplans[0], "_stack_arena", None)
             if st is None:
                 st = bplans[0]._stack_arena = StackArena()
-            cps, o2 = [], 0
-            for k in range(nb):
-                cps.append(FlowBlockPlan.conv_params(params[o2: o2 + counts[k]], n_layers))
-                o2 += counts[k]
-            st.pack([bp.plan for bp in bplans], cps, 2 + 2 * n_layers, tag=io)
-        # W^-1 and log det W of every block's invertible 1x1 convolution: one launch (a table of the weights' addresses, cached)
-        stack_prep = _STACK_PACK and nb > 1
-        if stack_prep and not w_reuse:
-            o2, wkey = 0, []
-            for k in range(nb):
-                wkey.append(params[o2 + 2].data_ptr())
-                o2 += counts[k]
+            st.pack([bp.plan for bp in bplans], [FlowBlockPlan.conv_params(pk, n_layers) for pk in pks], 2 + 2 * n_layers, tag=io)
+        # ... and W^-1 and log det W of every block's invertible 1x1 convolution (a table of the weights' addresses, cached)
+        if stack_pack and not w_reuse:
             wtab = getattr(bplans[0], "_w_table", None)
-            if wtab is None or wtab[0] != wkey:
-                wtab = bplans[0]._w_table = (wkey, torch.tensor(wkey, dtype=torch.int64).to(dev))
-            call("glowtts_invconv_prepare_multi", ptr(wtab[1]), pw, n_split * n_split + 1, nb, n_split)
+            if wtab is None or wtab[0] != w_ptrs:
+                wtab = bplans[0]._w_table = (w_ptrs, torch.tensor(w_ptrs, dtype=torch.int64).to(dev))
+            call("glowtts_invconv_prepare_multi", ptr(wtab[1]), ptr(winv), n_split * n_split + 1, nb, n_split)
         # Two half-batch chains on two streams (forward only; fp32 tensors with the boundary launch): every utterance is independent in
         # the forward, and two DIFFERENT kernels sharing the CUs fill each other's prologues and epilogues where two workgroups of
         # one kernel run in lock-step (tools/halfbatch_probe.py: a WN stack's forward 272 -> 245 us).  Same kernels, same slabs — a
         # call covers B / 2 utterances of every slab (tab.reserved = utterances per layer slab) —, results bit for bit the same.
-        halves = _FWD_CHAINS if (_HALF_BATCH_FWD and boundary and stack_prep and stack_pack and B % _FWD_CHAINS == 0
+        halves = _FWD_CHAINS if (_HALF_BATCH_FWD and boundary and stack_pack and B % _FWD_CHAINS == 0
                                  and os.environ.get("GLOWTTS_SIDE_STREAM", "1") != "0"       # (one-stream profiling passes)
                                  ) else 1
+        chains = [call]                                           # one chain: every launch on the current stream
         if halves > 1:
             main_s = torch.cuda.current_stream(dev)
             extra = [_hip.side_stream(dev, "fwd%d" % (j + 2)) for j in range(halves - 1)]
             for s2 in extra:
                 s2.wait_stream(main_s)
-                for t_ in (x, m2, x_len, zs, y, out, h0, skip, acts, ts, xs, logdets, winv, drops):
-                    if t_ is not None:
-                        t_.record_stream(s2)
-            chains, Bh = [main_s.cuda_stream] + [s2.cuda_stream for s2 in extra], B // halves
-        off = 0
+                _record_for_wgrad(s2, x, m2, x_len, zs, y, out, h0, skip, acts, ts, xs, logdets, winv, drops)
+            chains = [functools.partial(_hip.call_on, s2.cuda_stream) for s2 in [main_s] + extra]      # (no stream context switches)
+        Bh, sig_i = B // halves, int(sigmoid_scale)
+        Y, H0, SKIP, OUT = FlowSlabs.LEAD_Y, FlowSlabs.LEAD_H0, FlowSlabs.LEAD_SKIP, FlowSlabs.LEAD_OUT
+        prev_tab, prevs = None, [None] * halves
         for k in range(nb):
-            pk = params[off: off + counts[k]]
-            off += counts[k]
-            bplan = bplans[k]
+            pk, bplan = pks[k], bplans[k]
             plan = bplan.plan
             if not stack_pack:
                 plan.ensure(FlowBlockPlan.conv_params(pk, n_layers), n_convs=2 + 2 * n_layers)
@@ -1489,60 +1568,39 @@ class FlowStackFn(Function):
             bound = bplan.bind(io)
             try:
                 tab = bplan.table(pk, n_layers)
-                tab.w_inv = pw + k * (n_split * n_split + 1) * 4
-                tab.logdet_w = tab.w_inv + 4 * n_split * n_split
+                curs = [slabs.block(k, hh * Bh, Bh) for hh in range(halves)]       # (per chain: its utterances of every slab)
+                tab.w_inv, tab.logdet_w = curs[0][3:5]
                 tab.reserved = B if halves > 1 else 0    # utterances per layer slab when a call covers only a part of them
-                flags = int(io) | (FB_W_READY if (stack_prep or w_reuse) else 0)
-                if halves > 1:
-                    flags |= (FB_SKIP_HEAD | FB_SKIP_START if k > 0 else 0) | (FB_SKIP_TAIL | FB_SKIP_END if k < nb - 1 else 0)
-                    sig_i = int(sigmoid_scale)
-                    for hh in range(halves):
-                        st, hb = chains[hh], hh * Bh
-                        oC, oH, oB, oM = hb * C * T * 4, hb * H * T * 4, hb * 4, hb * T * 4
-                        if k > 0:
-                            _hip.call_on(st, "glowtts_flow_boundary_fwd", psk + (k - 1) * nH * 4 + oH, prev_tab.wf_end, prev_tab.b_end,
-                                         py + (k - 1) * nC * 4 + oC, pm + oM, ptr(pk[0]), ptr(pk[1]), ptr(pk[2]), tab.logdet_w, pl + oB,
-                                         tab.wf_start, tab.b_start, po + (k - 1) * nC * 4 + oC, py + k * nC * 4 + oC, ph + k * nH * 4 + oH,
-                                         pld + (k - 1) * B * 4 + oB, pld + k * B * 4 + oB, Bh, C, H, T, n_split, sig_i)
-                        _hip.call_on(st, "glowtts_flow_block_fwd_io", ctypes.addressof(tab),
-                                     (px if k == 0 else pz + (k - 1) * nC * 4) + oC, pm + oM, pl + oB, None,
-                                     None if pdr is None else pdr + k * n_layers * 2 * nH + hb * 2 * H * T, scale, py + k * nC * 4 + oC, None,
-                                     ph + k * nH * 4 + oH, pxs + k * nx * nH * 4 + oH if n_layers > 1 else None,
-                                     pa + k * n_layers * nH * 4 + oH, pts + k * n_layers * 2 * nH * 4 + 2 * oH, psk + k * nH * 4 + oH,
-                                     po + k * nC * 4 + oC, pz + k * nC * 4 + oC, pld + k * B * 4 + oB, Bh, C, H, T, taps, dil_rate, n_split,
-                                     sig_i, flags)
-                    tab.reserved = 0                 # (read by the calls above while they queued their launches; the table is cached)
-                    prev_tab = tab
-                    continue
-                if fuse and k > 0 and not stack_prep and not w_reuse:
-                    call("glowtts_invconv_prepare", ptr(pk[2]), tab.w_inv, tab.logdet_w, n_split)
-                if boundary and k > 0:
-                    call("glowtts_flow_boundary_fwd", psk + (k - 1) * nH * 4, prev_tab.wf_end, prev_tab.b_end, py + (k - 1) * nC * 4, pm,
-                         ptr(pk[0]), ptr(pk[1]), ptr(pk[2]), tab.logdet_w, pl, tab.wf_start, tab.b_start, po + (k - 1) * nC * 4,
-                         py + k * nC * 4, ph + k * nH * 4, pld + (k - 1) * B * 4, pld + k * B * 4, B, C, H, T, n_split,
-                         int(sigmoid_scale))
-                    flags |= FB_SKIP_HEAD | FB_SKIP_START
-                elif fuse and k > 0:
-                    call("glowtts_coupling_actnorm_invconv_fwd", py + (k - 1) * nC * 4, po + (k - 1) * nC * 4, pm, ptr(pk[0]), ptr(pk[1]),
-                         ptr(pk[2]), tab.logdet_w, pl, py + k * nC * 4, pld + (k - 1) * B * 4, pld + k * B * 4, B, C, T, n_split,
-                         int(sigmoid_scale))
-                    flags |= FB_SKIP_HEAD
+                flags = int(io) | (FB_W_READY if (stack_pack or w_reuse) else 0)
+                if fuse and k > 0:
+                    logs, bias, w = ptr(pk[0]), ptr(pk[1]), ptr(pk[2])
+                    if not stack_pack and not w_reuse:
+                        call("glowtts_invconv_prepare", w, tab.w_inv, tab.logdet_w, n_split)
+                    flags |= FB_SKIP_HEAD | (FB_SKIP_START if boundary else 0)
                 if fuse and k < nb - 1:
                     flags |= FB_SKIP_TAIL | (FB_SKIP_END if boundary else 0)
+                for queue, cur, prev in zip(chains, curs, prevs):      # (the chains need the boundary launch: without it, one chain)
+                    lead, pz, pld, _, logdet_w, _ = cur
+                    if fuse and k > 0:
+                        lead_p, _, pld_p = prev[:3]
+                        if boundary:
+                            queue("glowtts_flow_boundary_fwd", lead_p[SKIP], prev_tab.wf_end, prev_tab.b_end, lead_p[Y], lead[1],
+                                   logs, bias, w, logdet_w, lead[2], tab.wf_start, tab.b_start, lead_p[OUT], lead[Y], lead[H0], pld_p,
+                                   pld, Bh, C, H, T, n_split, sig_i)
+                        else:
+                            call("glowtts_coupling_actnorm_invconv_fwd", lead_p[Y], lead_p[OUT], lead[1], logs, bias, w, logdet_w,
+                                 lead[2], lead[Y], pld_p, pld, B, C, T, n_split, sig_i)
+                    queue("glowtts_flow_block_fwd_io", ctypes.addressof(tab), *lead[:3], None, *lead[3:], pz, pld, Bh, C, H, T,
+                           taps, dil_rate, n_split, sig_i, flags)
+                prevs = curs
+                tab.reserved = 0                         # (read by the calls above while they queued their launches; the table is cached)
                 prev_tab = tab
-                call("glowtts_flow_block_fwd_io", ctypes.addressof(tab), px if k == 0 else pz + (k - 1) * nC * eF, pm, pl, None,
-                     None if pdr is None else pdr + k * n_layers * 2 * nH, scale, py + k * nC * eF,
-                     None if py0 is None else py0 + k * (nC // 2) * eA, ph + k * nH * eA,
-                     pxs + k * nx * nH * eA if n_layers > 1 else None, pa + k * n_layers * nH * eA,
-                     pts + k * n_layers * 2 * nH * eA, psk + k * nH * eA, po + k * nC * 4, pz + k * nC * eF, pld + k * B * 4, B, C, H, T,
-                     taps, dil_rate, n_split, int(sigmoid_scale), flags)
             finally:
                 bplan.unbind(bound)
         if halves > 1:
             for s2 in extra:
                 main_s.wait_stream(s2)
-        ctx.save_for_backward(x, m2, x_len, zs, y, h0, acts, ts, skip, out, winv, xs, *([] if drops is None else [drops]),
-                              *([] if y0h is None else [y0h]))
+        _save_tensors(ctx, x, m2, x_len, zs, y, h0, acts, ts, skip, out, winv, xs, drops, y0h)
         ctx.cfg, ctx.bplans, ctx.counts, ctx.params, ctx.taps, ctx.scale, ctx.fuse = cfg, bplans, counts, params, taps, scale, fuse
         ctx.boundary = boundary
         return zs[nb - 1], logdets.sum(0)
@@ -1550,116 +1608,86 @@ class FlowStackFn(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dz, dlogdet):
-        import ctypes
         n_split, sigmoid_scale, p_drop, dil_rate, n_layers, H, io = ctx.cfg
-        fdt = torch.bfloat16 if io & 2 else torch.float32
-        adt = torch.bfloat16 if io & 1 else torch.float32
-        eF, eA = (2 if io & 2 else 4), (2 if io & 1 else 4)
-        sv = list(ctx.saved_tensors)
-        x, m2, x_len, zs, y, h0, acts, ts, skip, out, winv, xs = sv[:12]
-        rest = sv[12:]
-        drops = rest.pop(0) if p_drop > 0 else None
-        y0h = rest.pop(0) if io == 1 else None
-        params, bplans, counts = ctx.params, ctx.bplans, ctx.counts
+        fdt, adt = _flow_dtypes(io)
+        x, m2, x_len, zs, y, h0, acts, ts, skip, out, winv, xs, drops, y0h = _saved_tensors(ctx)
+        params, bplans = ctx.params, ctx.bplans
         nb = len(bplans)
         B, C, T = x.shape
         dev = x.device
-        if not all(p.grad is not None and p.grad.is_contiguous() for p in params):
-            raise RuntimeError("FlowStackFn.backward: a parameter gradient buffer disappeared between forward and backward")
+        _check_grad_buffers("FlowStackFn.backward", params)
         act = lambda *shape: torch.empty(shape, device=dev, dtype=adt)                                # noqa: E731
         flow = lambda *shape: torch.empty(shape, device=dev, dtype=fdt)                               # noqa: E731
-        dz = dz.contiguous() if dz is not None else torch.zeros_like(x)
-        if dz.dtype != fdt:
-            dz = dz.to(fdt)
-        dlogdet = dlogdet.contiguous().float() if dlogdet is not None else torch.zeros(B, device=dev)
+        dz, dlogdet = _flow_grad_inputs(dz, dlogdet, x, io)
         wgrad = _WgradStream(dev)
-        two_src = (not io) and dil_rate == 1 and H % 192 == 0 and T % 4 == 0
+        two_src = _two_src(io, dil_rate, H, T)
         # per-block scratch as slices of one allocation per kind: the weight-gradient stream reads a block's scratch after the
         # chain has moved on to the next block, so nothing is shared between blocks
         dy, dout, dxs = flow(nb, B, C, T), act(nb, B, C, T), flow(nb, B, C, T)
         dskip = act(nb, B, H, T)
         d_rs = act(nb, B, H, T) if two_src else act(nb, n_layers, B, 2 * H, T)
         d_xin, dx_wn = act(nb, n_layers, B, 2 * H, T), act(nb, n_layers, B, H, T)
-        nC, nH = B * C * T, B * H * T
-        nx = max(n_layers - 1, 1)
-        px, pm, pl = ptr(x), ptr(m2), ptr(x_len)
-        pz, py, po, ph, psk, py0 = ptr(zs), ptr(y), ptr(out), ptr(h0), ptr(skip), ptr(y0h)
-        pa, pts, pxs, pw = ptr(acts), ptr(ts), ptr(xs), ptr(winv)
-        pdr = ptr(drops)
-        pdy, pdo, pdx, pds, pdrs, pdxin, pdxw = ptr(dy), ptr(dout), ptr(dxs), ptr(dskip), ptr(d_rs), ptr(d_xin), ptr(dx_wn)
-        pdz, pdl = ptr(dz), ptr(dlogdet)
-        drs_stride = (nH if two_src else n_layers * 2 * nH) * eA
+        slabs = FlowSlabs(nb, n_layers, B, C, H, T, io, n_split, ctx.scale,
+                          [ptr(t) for t in (x, m2, x_len, drops, y, y0h, h0, xs, acts, ts, skip, out, zs)] + [None, ptr(winv)],
+                          two_src, [ptr(t) for t in (dz, dlogdet, dy, dout, dskip, d_rs, d_xin, dx_wn, dxs)])
+        pm, pl, pdl = slabs.ptrs[1], slabs.ptrs[2], slabs.grad_ptrs[1]
         side = wgrad.side.cuda_stream if wgrad.enabled else None
-        offs = [0]
-        for c in counts:
-            offs.append(offs[-1] + c)
+        pks = _split_params(params, ctx.counts)
         if wgrad.enabled:                                # read by the second stream after this returns
-            for t in (y, y0h, h0, xs, acts, skip, dout, dskip, d_rs, d_xin, dx_wn, zs, m2):    # (m2: see FlowBlockFn.backward)
-                if t is not None:
-                    t.record_stream(wgrad.side)
+            _record_for_wgrad(wgrad.side, y, y0h, h0, xs, acts, skip, dout, dskip, d_rs, d_xin, dx_wn, zs, m2)
         # between blocks (fp32 tensors): start conv backward-data(k) + ActNorm / InvConv backward(k) + coupling backward(k - 1) + end conv
         # backward-data(k - 1) as ONE launch on the chain (csrc/flow_boundary.hip); the ActNorm / InvConv parameter gradients come out
         # as per-workgroup partials, added up by a small launch behind the block's weight gradients
-        boundary = ctx.fuse and ctx.boundary and _FLOW_BOUNDARY_BWD
+        fuse = ctx.fuse
+        boundary = fuse and ctx.boundary and _FLOW_BOUNDARY_BWD
         if boundary:
             n_part = B * ((T + 31) // 32) * (C // n_split) * (2 * n_split + n_split * n_split)
             part = torch.empty(nb - 1, n_part, device=dev, dtype=torch.float32)
             ppart = ptr(part)
             if wgrad.enabled:
-                part.record_stream(wgrad.side)
+                _record_for_wgrad(wgrad.side, part)
+        Y, OUT = FlowSlabs.LEAD_Y, FlowSlabs.LEAD_OUT
+        below = slabs.block(nb - 1)
         for k in range(nb - 1, -1, -1):
-            pk = params[offs[k]: offs[k + 1]]
-            bplan = bplans[k]
+            pk, bplan = pks[k], bplans[k]
             on_side = wgrad.enabled and k >= _WGRAD_MAIN_BLOCKS      # the backward's last blocks keep their weight gradients on the chain
             tab = bplan.table(pk, n_layers)
-            tab.w_inv = pw + k * (n_split * n_split + 1) * 4
-            tab.logdet_w = tab.w_inv + 4 * n_split * n_split
-            fuse = ctx.fuse
+            lead, _, _, tab.w_inv, tab.logdet_w, grads = below
             flags = int(io) | (FB_SKIP_HEAD if fuse and k > 0 else 0) | (FB_SKIP_TAIL if fuse and k < nb - 1 else 0)
             if boundary:
                 flags |= (FB_SKIP_START if k > 0 else 0) | (FB_SKIP_END if k < nb - 1 else 0)
             bound = bplan.bind(io)
             try:
-                call("glowtts_flow_block_bwd_io", ctypes.addressof(tab), px if k == 0 else pz + (k - 1) * nC * eF, pm, pl,
-                     None if pdr is None else pdr + k * n_layers * 2 * nH, ctx.scale, py + k * nC * eF,
-                     None if py0 is None else py0 + k * (nC // 2) * eA, ph + k * nH * eA,
-                     pxs + k * nx * nH * eA if n_layers > 1 else None, pa + k * n_layers * nH * eA,
-                     pts + k * n_layers * 2 * nH * eA, psk + k * nH * eA, po + k * nC * 4,
-                     pdz if k == nb - 1 else pdx + (k + 1) * nC * eF, pdl, pdy + k * nC * eF, pdo + k * nC * eA, pds + k * nH * eA,
-                     pdrs + k * drs_stride, pdxin + k * n_layers * 2 * nH * eA, pdxw + k * n_layers * nH * eA, pdx + k * nC * eF, None,
-                     B, C, H, T, ctx.taps, dil_rate, n_split, int(sigmoid_scale), int(two_src), flags, side if on_side else None)
+                call("glowtts_flow_block_bwd_io", ctypes.addressof(tab), *lead, *grads, None, B, C, H, T, ctx.taps, dil_rate, n_split,
+                     int(sigmoid_scale), int(two_src), flags, side if on_side else None)
             finally:
                 bplan.unbind(bound)
             live = [p for p in pk if p is not None]
             _mark_direct(live, True)
             ai_late = fuse and k > 0                     # logs / bias / W of this block: their gradients come from the fused kernel below
-            conv_live = live[3:] if ai_late else live
-            if on_side:
-                with torch.cuda.stream(wgrad.side):      # every gradient of the block is complete at this point of THAT stream
-                    _notify(conv_live)
-            else:
-                _notify(conv_live)
-            if ai_late and boundary:
-                tab_prev = bplans[k - 1].table(params[offs[k - 1]: offs[k]], n_layers)
+            _notify_on(wgrad.side if on_side else None, live[3:] if ai_late else live)
+            if k > 0:
+                below = slabs.block(k - 1)
+            if not ai_late:
+                continue
+            lead_p, grads_p = below[0], below[5]
+            pdy, pdy_p, pdo_p, pds_p = grads[2], grads_p[2], grads_p[3], grads_p[4]
+            if boundary:
+                tab_prev = bplans[k - 1].table(pks[k - 1], n_layers)
                 pp = ppart + (k - 1) * n_part * 4
-                call("glowtts_flow_boundary_bwd", pdxw + k * n_layers * nH * 4, tab.wb_start, pdy + k * nC * 4, py + (k - 1) * nC * 4,
-                     po + (k - 1) * nC * 4, pm, ptr(pk[0]), ptr(pk[1]), ptr(pk[2]), pdl, tab_prev.wb_end, pdy + (k - 1) * nC * 4,
-                     pdo + (k - 1) * nC * 4, pds + (k - 1) * nH * 4, pp, B, C, H, T, n_split, int(sigmoid_scale), int(two_src))
+                call("glowtts_flow_boundary_bwd", grads[7], tab.wb_start, pdy, lead_p[Y], lead_p[OUT], pm, ptr(pk[0]), ptr(pk[1]),
+                     ptr(pk[2]), pdl, tab_prev.wb_end, pdy_p, pdo_p, pds_p, pp, B, C, H, T, n_split, int(sigmoid_scale), int(two_src))
                 if on_side:
                     wgrad.side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(wgrad.side):
-                        call("glowtts_flow_boundary_bwd_reduce", pp, tab.w_inv, pdl, pl, ptr(pk[0].grad), ptr(pk[1].grad),
-                             ptr(pk[2].grad), B, C, T, n_split)
-                        _notify(live[:3])
-                else:
+                with torch.cuda.stream(wgrad.side if on_side else None):             # (None: the stream stays as it is)
                     call("glowtts_flow_boundary_bwd_reduce", pp, tab.w_inv, pdl, pl, ptr(pk[0].grad), ptr(pk[1].grad), ptr(pk[2].grad),
                          B, C, T, n_split)
                     _notify(live[:3])
-            elif ai_late:
+            else:
                 # block k's ActNorm + InvConv backward fused with block k - 1's coupling backward: dy_k -> dy_{k-1}, dout_{k-1}
-                call("glowtts_coupling_actnorm_invconv_bwd", py + (k - 1) * nC * 4, po + (k - 1) * nC * 4, pm, ptr(pk[0]), ptr(pk[1]),
-                     ptr(pk[2]), tab.w_inv, pdy + k * nC * 4, pdl, pl, pdy + (k - 1) * nC * 4, pdo + (k - 1) * nC * 4, ptr(pk[0].grad),
-                     ptr(pk[1].grad), ptr(pk[2].grad), B, C, T, n_split, int(sigmoid_scale))
+                call("glowtts_coupling_actnorm_invconv_bwd", lead_p[Y], lead_p[OUT], pm, ptr(pk[0]), ptr(pk[1]), ptr(pk[2]), tab.w_inv,
+                     pdy, pdl, pl, pdy_p, pdo_p, ptr(pk[0].grad), ptr(pk[1].grad), ptr(pk[2].grad), B, C, T, n_split,
+                     int(sigmoid_scale))
                 _notify(live[:3])
         return (dxs[0], None, None, None, None, None, None) + (None,) * ctx.n_param_args
 
@@ -1736,205 +1764,170 @@ def encoder_layer_eligible(group, attn, ffn, norm1, norm2, x) -> bool:
     return all(p.requires_grad and p.grad is not None and p.grad.is_contiguous() for p in params)
 
 
+class EncLayerSlabs:
+    """One transformer layer's activation buffer [q k v y_att o x1 y2 x2 | h | p_attn | stats1 stats2] and backward workspace
+    [dx1a dy2 dx1 dxa d_o dy_att dq dk dv dx | d_pre | ds], fp32, as byte offsets (`act`, `ws`: name -> offset) — the ONE
+    statement of that layout, for EncoderLayerFn (one layer) and EncoderStackFn (`per` / `wper` floats per layer of its two
+    slabs) — and the two native calls queued from it.  The keep-masks of a layer's four dropouts lie as bytes
+    [attention (B,h,T,T) | branch 1 (B,H,T) | FFN (B,F,T) | branch 2 (B,H,T)], `ksz` of them per layer."""
+
+    def __init__(self, B, H, F_, T, cfg):
+        self.cfg = cfg
+        heads = cfg[0]
+        n_ht, n_ft, n_tt = B * H * T, B * F_ * T, B * heads * T * T
+        acts = [(n, n_ht, (B, H, T)) for n in ("q", "k", "v", "y_att", "o", "x1", "y2", "x2")]
+        acts += [("h", n_ft, (B, F_, T)), ("p_attn", n_tt, (B, heads, T, T)), ("stats1", 2 * B * T, (B, 2, T)),
+                 ("stats2", 2 * B * T, (B, 2, T))]
+        work = [(n, n_ht, (B, H, T)) for n in ("dx1a", "dy2", "dx1", "dxa", "d_o", "dy_att", "dq", "dk", "dv", "dx")]
+        work += [("d_pre", n_ft, (B, F_, T)), ("ds", n_tt, (B, heads, T, T))]
+        self.act, self.ws, self.shape = {}, {}, {}
+        self.per = self._lay(acts, self.act)                   # floats of one layer's activations
+        self.wper = self._lay(work, self.ws)                   # floats of one layer's backward workspace
+        self.keep_offsets = (0, n_tt, n_tt + n_ht, n_tt + n_ht + n_ft)
+        self.ksz = n_tt + n_ht + n_ft + n_ht
+        # the regions in the order the two entry points take them, and their trailing scalars
+        a, w = self.act, self.ws
+        self.fwd_act = [a[n] for n in ("q", "k", "v", "p_attn", "y_att", "o", "x1", "stats1", "h", "y2", "x2", "stats2")]
+        self.bwd_act = [a[n] for n in ("q", "k", "v", "p_attn", "y_att", "o", "x1", "stats1", "h", "y2", "stats2")]
+        self.bwd_ws = [w[n] for n in ("dx1a", "dy2", "d_pre", "dx1", "dxa", "d_o", "dy_att", "ds", "dq", "dk", "dv", "dx")]
+        self.scalars = (B, H, F_, T, *cfg[:5])                 # ..., heads, taps, window, share, blk
+
+    def _lay(self, parts, table):
+        floats = 0
+        for name, n, shape in parts:
+            table[name], self.shape[name] = 4 * floats, (floats, n, shape)
+            floats += n
+        return floats
+
+    def view(self, flat, name):
+        """Region `name` of one layer's (flat) activation buffer or workspace, in its shape."""
+        first, n, shape = self.shape[name]
+        return flat[first: first + n].view(shape)
+
+    def keeps(self, base):
+        """The four keep-mask pointers of the layer whose masks start at `base` (None: no dropout)."""
+        return (None,) * 4 if base is None else [base + o for o in self.keep_offsets]
+
+    def fwd(self, tab, base, x_in, m2, keeps, scale):
+        call("glowtts_encoder_layer_fwd", ctypes.addressof(tab), x_in, m2, *keeps, scale, *[base + o for o in self.fwd_act],
+             *self.scalars, float(self.cfg[5]))
+
+    def bwd(self, tab, base, wbase, x_in, d_in, m2, keeps, scale, side):
+        call("glowtts_encoder_layer_bwd", ctypes.addressof(tab), x_in, m2, *keeps, scale, *[base + o for o in self.bwd_act], d_in,
+             *[wbase + o for o in self.bwd_ws], *self.scalars, side)
+
+
+_enc_slabs = functools.lru_cache(maxsize=64)(EncLayerSlabs)         # (a training run sees few shapes: built once per shape)
+
+
+def _enc_wgrad(dev):
+    # The layers' weight-gradient kernels stay on the stream the backward runs on (the text encoder's own side stream,
+    # which has ~10 ms of decoder backward to hide ~3 ms of work): sent to the decoder's weight-gradient stream they queue
+    # behind its 5-tap kernels and lengthen the tail every step ends with (A/B: +0.4 ms per step).
+    wgrad = _WgradStream(dev)
+    wgrad.enabled = wgrad.enabled and _ENC_WGRAD
+    return wgrad
+
+
 class EncoderStackFn(Function):
     """ALL post-LN transformer layers of the text encoder (reference attentions.py:63-73: the loop over the layers) as ONE
     autograd node (round 4): EncoderLayerFn's native call per layer, but one activation buffer, one workspace, one saved-tensor
-    list and one node for the stack — the layers' slices are addressed by pointer arithmetic.  `keep`: the byte keep-masks of all
-    four dropouts of all layers, laid out layer by layer as [attention (B,h,T,T) | branch 1 (B,H,T) | FFN (B,F,T) | branch 2
-    (B,H,T)], or None."""
+    list and one node for the stack — the layers' slices are addressed through EncLayerSlabs.  `keep`: the byte keep-masks of all
+    four dropouts of all layers, laid out layer by layer (EncLayerSlabs), or None."""
 
     @staticmethod
     def forward(ctx, x, m2, keep, cfg, layers, counts, *params):
-        import ctypes
         params, ctx.n_param_args = _unpack_params(params)
-        heads, taps, window, share, blk, eps, p_drop = cfg
         nl = len(layers)
         x = f32(x.contiguous())
         B, H, T = x.shape
-        F_ = layers[0][2].filter_channels
-        dev = x.device
-        n_ht, n_ft, n_tt = B * H * T, B * F_ * T, B * heads * T * T
-        per = 8 * n_ht + n_ft + n_tt + 4 * B * T                  # floats of one layer's activations (EncoderLayerFn's layout)
-        buf = torch.empty(nl, per, device=dev, dtype=torch.float32)
-        scale = 1.0 / (1.0 - p_drop) if keep is not None else 1.0
+        L = _enc_slabs(B, H, layers[0][2].filter_channels, T, cfg)
+        buf = torch.empty(nl, L.per, device=x.device, dtype=torch.float32)
+        scale = 1.0 / (1.0 - cfg[6]) if keep is not None else 1.0
         pk_, pb, px, pm = ptr(keep), ptr(buf), ptr(x), ptr(m2)
-        ksz = n_tt + n_ht + n_ft + n_ht                            # keep bytes of one layer
-        o_q, o_k, o_v, o_ya, o_o, o_x1, o_y2, o_x2 = (4 * j * n_ht for j in range(8))
-        o_h = 4 * 8 * n_ht
-        o_p = o_h + 4 * n_ft
-        o_s1 = o_p + 4 * n_tt
-        o_s2 = o_s1 + 4 * 2 * B * T
         for l, (group, attn, ffn, norm1, norm2) in enumerate(layers):
             tab, _ = _enc_layer_table(group, attn, ffn, norm1, norm2)
-            base = pb + 4 * l * per
-            xin = px if l == 0 else pb + 4 * (l - 1) * per + o_x2
-            kb = None if pk_ is None else pk_ + l * ksz
+            xin = px if l == 0 else pb + 4 * (l - 1) * L.per + L.act["x2"]
             bound = group.plan.bind()                    # the FFN convolutions take the group's bf16 planes (conv arithmetic)
             try:
-                call("glowtts_encoder_layer_fwd", ctypes.addressof(tab), xin, pm, kb, None if kb is None else kb + n_tt,
-                     None if kb is None else kb + n_tt + n_ht, None if kb is None else kb + n_tt + n_ht + n_ft, scale,
-                     base + o_q, base + o_k, base + o_v, base + o_p, base + o_ya, base + o_o, base + o_x1, base + o_s1, base + o_h,
-                     base + o_y2, base + o_x2, base + o_s2, B, H, F_, T, heads, taps, window, share, blk, float(eps))
+                L.fwd(tab, pb + 4 * l * L.per, xin, pm, L.keeps(None if pk_ is None else pk_ + l * L.ksz), scale)
             finally:
                 WNPackPlan.unbind(bound)
-            attn.attn = buf[l, (o_p // 4): (o_p // 4) + n_tt].view(B, heads, T, T).detach()
-        ctx.save_for_backward(x, m2, buf, *([] if keep is None else [keep]))
-        ctx.cfg, ctx.layers, ctx.counts, ctx.dims, ctx.scale, ctx.params = cfg, layers, counts, (B, H, F_, T), scale, params
-        return buf[nl - 1, (o_x2 // 4): (o_x2 // 4) + n_ht].view(B, H, T)
+            attn.attn = L.view(buf[l], "p_attn").detach()
+        _save_tensors(ctx, x, m2, buf, keep)
+        ctx.slabs, ctx.layers, ctx.scale, ctx.params = L, layers, scale, params
+        return L.view(buf[nl - 1], "x2")
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dx_out):
-        import ctypes
-        heads, taps, window, share, blk, eps, p_drop = ctx.cfg
-        layers, counts, params = ctx.layers, ctx.counts, ctx.params
+        L, layers = ctx.slabs, ctx.layers
         nl = len(layers)
-        B, H, F_, T = ctx.dims
-        sv = ctx.saved_tensors
-        x, m2, buf = sv[:3]
-        keep = sv[3] if len(sv) > 3 else None
-        dev = x.device
-        n_ht, n_ft, n_tt = B * H * T, B * F_ * T, B * heads * T * T
-        per = 8 * n_ht + n_ft + n_tt + 4 * B * T
-        wper = 10 * n_ht + n_ft + n_tt                            # floats of one layer's backward workspace
-        ws = torch.empty(nl, wper, device=dev, dtype=torch.float32)
+        x, m2, buf, keep = _saved_tensors(ctx)
+        ws = torch.empty(nl, L.wper, device=x.device, dtype=torch.float32)
         dx_out = f32(dx_out.contiguous())
-        wgrad = _WgradStream(dev)
-        wgrad.enabled = wgrad.enabled and _ENC_WGRAD          # (see EncoderLayerFn.backward: the weight gradients stay on this stream)
+        wgrad = _enc_wgrad(x.device)
         pk_, pb, px, pm, pw, pdo = ptr(keep), ptr(buf), ptr(x), ptr(m2), ptr(ws), ptr(dx_out)
-        ksz = n_tt + n_ht + n_ft + n_ht
-        o_q, o_k, o_v, o_ya, o_o, o_x1, o_y2, o_x2 = (4 * j * n_ht for j in range(8))
-        o_h = 4 * 8 * n_ht
-        o_p = o_h + 4 * n_ft
-        o_s1 = o_p + 4 * n_tt
-        o_s2 = o_s1 + 4 * 2 * B * T
-        w_dx1a, w_dy2, w_dx1, w_dxa, w_do, w_dya, w_dq, w_dk, w_dv, w_dx = (4 * j * n_ht for j in range(10))
-        w_dpre = 4 * 10 * n_ht
-        w_ds = w_dpre + 4 * n_ft
         side = wgrad.side.cuda_stream if wgrad.enabled else None
-        offs = [0]
-        for c in counts:
-            offs.append(offs[-1] + c)
         if wgrad.enabled:
-            for t in (x, buf, ws, dx_out, m2, keep):         # (masks too: see FlowBlockFn.backward)
-                if t is not None:
-                    t.record_stream(wgrad.side)
+            _record_for_wgrad(wgrad.side, x, buf, ws, dx_out, m2, keep)
         for l in range(nl - 1, -1, -1):
             group, attn, ffn, norm1, norm2 = layers[l]
             tab, live = _enc_layer_table(group, attn, ffn, norm1, norm2)
-            base, wb = pb + 4 * l * per, pw + 4 * l * wper
-            xin = px if l == 0 else pb + 4 * (l - 1) * per + o_x2
-            din = pdo if l == nl - 1 else pw + 4 * (l + 1) * wper + w_dx
-            kb = None if pk_ is None else pk_ + l * ksz
+            xin = px if l == 0 else pb + 4 * (l - 1) * L.per + L.act["x2"]
+            din = pdo if l == nl - 1 else pw + 4 * (l + 1) * L.wper + L.ws["dx"]
             bound = group.plan.bind()
             try:
-                call("glowtts_encoder_layer_bwd", ctypes.addressof(tab), xin, pm, kb, None if kb is None else kb + n_tt,
-                     None if kb is None else kb + n_tt + n_ht, None if kb is None else kb + n_tt + n_ht + n_ft, ctx.scale,
-                     base + o_q, base + o_k, base + o_v, base + o_p, base + o_ya, base + o_o, base + o_x1, base + o_s1, base + o_h,
-                     base + o_y2, base + o_s2, din, wb + w_dx1a, wb + w_dy2, wb + w_dpre, wb + w_dx1, wb + w_dxa, wb + w_do,
-                     wb + w_dya, wb + w_ds, wb + w_dq, wb + w_dk, wb + w_dv, wb + w_dx, B, H, F_, T, heads, taps, window, share,
-                     blk, side)
+                L.bwd(tab, pb + 4 * l * L.per, pw + 4 * l * L.wper, xin, din, pm, L.keeps(None if pk_ is None else pk_ + l * L.ksz),
+                      ctx.scale, side)
             finally:
                 WNPackPlan.unbind(bound)
             _mark_direct(live, True)
-            if wgrad.enabled:
-                with torch.cuda.stream(wgrad.side):
-                    _notify(live)
-            else:
-                _notify(live)
-        return (ws[0, (w_dx // 4): (w_dx // 4) + n_ht].view(B, H, T), None, None, None, None, None) + (None,) * ctx.n_param_args
+            _notify_on(wgrad.side if wgrad.enabled else None, live)
+        return (L.view(ws[0], "dx"), None, None, None, None, None) + (None,) * ctx.n_param_args
 
 
 class EncoderLayerFn(Function):
     """One post-LN transformer layer of the text encoder (reference attentions.py:63-73, 204-264, 373-381) as ONE autograd
-    node: forward and backward are one native call each (csrc/wn_stack.hip: glowtts_encoder_layer_fwd / _bwd)."""
+    node: forward and backward are one native call each (csrc/wn_stack.hip: glowtts_encoder_layer_fwd / _bwd) — the one-layer
+    case of EncoderStackFn's slabs, with the four keep-masks as separate tensors."""
 
     @staticmethod
     def forward(ctx, x, m2, drops, cfg, mods, *params):
-        import ctypes
-        heads, taps, window, share, blk, eps, p_drop = cfg
         group, attn, ffn, norm1, norm2 = mods
         x = f32(x.contiguous())
         B, H, T = x.shape
-        F_ = ffn.filter_channels
-        dev = x.device
+        L = _enc_slabs(B, H, ffn.filter_channels, T, cfg)
         tab, live = _enc_layer_table(group, attn, ffn, norm1, norm2)
-        n_ht, n_ft, n_tt = B * H * T, B * F_ * T, B * heads * T * T
-        buf = torch.empty(8 * n_ht + n_ft + n_tt + 4 * B * T, device=dev, dtype=torch.float32)
-        off = [0]
-
-        def take(n, *shape):
-            v = buf[off[0]: off[0] + n].view(*shape)
-            off[0] += n
-            return v
-        q, k, v, y_att, o, x1, y2, x2 = (take(n_ht, B, H, T) for _ in range(8))
-        h = take(n_ft, B, F_, T)
-        p_attn = take(n_tt, B, heads, T, T)
-        stats1, stats2 = take(2 * B * T, B, 2, T), take(2 * B * T, B, 2, T)
-        da, do_, dh, d2 = drops if drops is not None else (None, None, None, None)
-        scale = 1.0 / (1.0 - p_drop) if drops is not None else 1.0
+        buf = torch.empty(L.per, device=x.device, dtype=torch.float32)
+        scale = 1.0 / (1.0 - cfg[6]) if drops is not None else 1.0
         bound = group.plan.bind()                        # the FFN convolutions take the group's bf16 planes (conv arithmetic)
         try:
-            call("glowtts_encoder_layer_fwd", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(da), ptr(do_), ptr(dh), ptr(d2), scale,
-                 ptr(q), ptr(k), ptr(v), ptr(p_attn), ptr(y_att), ptr(o), ptr(x1), ptr(stats1), ptr(h), ptr(y2), ptr(x2),
-                 ptr(stats2), B, H, F_, T, heads, taps, window, share, blk, float(eps))
+            L.fwd(tab, ptr(buf), ptr(x), ptr(m2), [ptr(d) for d in drops or (None,) * 4], scale)
         finally:
             WNPackPlan.unbind(bound)
-        attn.attn = p_attn.detach()
-        ctx.save_for_backward(x, m2, buf, *([] if drops is None else drops))
-        ctx.cfg, ctx.mods, ctx.dims, ctx.scale, ctx.live = cfg, mods, (B, H, F_, T), scale, live
-        return x2
+        attn.attn = L.view(buf, "p_attn").detach()
+        _save_tensors(ctx, x, m2, buf, *(drops or (None,) * 4))
+        ctx.slabs, ctx.mods, ctx.scale, ctx.live = L, mods, scale, live
+        return L.view(buf, "x2")
 
     @staticmethod
     @once_differentiable
     def backward(ctx, dx2):
-        import ctypes
-        heads, taps, window, share, blk, eps, p_drop = ctx.cfg
-        group, attn, ffn, norm1, norm2 = ctx.mods
-        B, H, F_, T = ctx.dims
-        sv = ctx.saved_tensors
-        x, m2, buf = sv[:3]
-        da, do_, dh, d2 = sv[3:7] if len(sv) > 3 else (None, None, None, None)
-        dev = x.device
-        n_ht, n_ft, n_tt = B * H * T, B * F_ * T, B * heads * T * T
-        off = [0]
-
-        def take(src, n, *shape):
-            v = src[off[0]: off[0] + n].view(*shape)
-            off[0] += n
-            return v
-        q, k, v, y_att, o, x1, y2, _x2 = (take(buf, n_ht, B, H, T) for _ in range(8))
-        h = take(buf, n_ft, B, F_, T)
-        p_attn = take(buf, n_tt, B, heads, T, T)
-        stats1, stats2 = take(buf, 2 * B * T, B, 2, T), take(buf, 2 * B * T, B, 2, T)
-        ws = torch.empty(10 * n_ht + n_ft + n_tt, device=dev, dtype=torch.float32)
-        off[0] = 0
-        dx1a, dy2, dx1, dxa, d_o, dy_att, dq, dk_, dv, dx = (take(ws, n_ht, B, H, T) for _ in range(10))
-        d_pre1 = take(ws, n_ft, B, F_, T)
-        ds = take(ws, n_tt, B, heads, T, T)
+        L = ctx.slabs
+        x, m2, buf, *drops = _saved_tensors(ctx)
+        ws = torch.empty(L.wper, device=x.device, dtype=torch.float32)
         dx2 = f32(dx2.contiguous())
-        tab, live = _enc_layer_table(group, attn, ffn, norm1, norm2)
-        # The layer's weight-gradient kernels stay on the stream this backward runs on (the text encoder's own side stream,
-        # which has ~10 ms of decoder backward to hide ~3 ms of work): sent to the decoder's weight-gradient stream they queue
-        # behind its 5-tap kernels and lengthen the tail every step ends with (A/B: +0.4 ms per step).
-        wgrad = _WgradStream(dev)
-        wgrad.enabled = wgrad.enabled and _ENC_WGRAD
-        bound = group.plan.bind()
+        tab, live = _enc_layer_table(*ctx.mods)
+        wgrad = _enc_wgrad(x.device)
+        if wgrad.enabled:
+            _record_for_wgrad(wgrad.side, x, buf, ws, dx2, m2, *drops)
+        bound = ctx.mods[0].plan.bind()
         try:
-            call("glowtts_encoder_layer_bwd", ctypes.addressof(tab), ptr(x), ptr(m2), ptr(da), ptr(do_), ptr(dh), ptr(d2), ctx.scale,
-                 ptr(q), ptr(k), ptr(v), ptr(p_attn), ptr(y_att), ptr(o), ptr(x1), ptr(stats1), ptr(h), ptr(y2), ptr(stats2),
-                 ptr(dx2), ptr(dx1a), ptr(dy2), ptr(d_pre1), ptr(dx1), ptr(dxa), ptr(d_o), ptr(dy_att), ptr(ds), ptr(dq), ptr(dk_),
-                 ptr(dv), ptr(dx), B, H, F_, T, heads, taps, window, share, blk,
-                 wgrad.side.cuda_stream if wgrad.enabled else None)
+            L.bwd(tab, ptr(buf), ptr(ws), ptr(x), ptr(dx2), ptr(m2), [ptr(d) for d in drops], ctx.scale,
+                  wgrad.side.cuda_stream if wgrad.enabled else None)
         finally:
             WNPackPlan.unbind(bound)
         _mark_direct(live, True)
-        if wgrad.enabled:
-            for t in (x, buf, ws, dx2, m2):              # read by the second stream after this returns (the mask too: see FlowBlockFn.backward)
-                if t is not None:
-                    t.record_stream(wgrad.side)
-            with torch.cuda.stream(wgrad.side):
-                _notify(live)
-        else:
-            _notify(live)
-        return (dx, None, None, None, None) + (None,) * len(live)
+        _notify_on(wgrad.side if wgrad.enabled else None, live)
+        return (L.view(ws, "dx"), None, None, None, None) + (None,) * len(live)

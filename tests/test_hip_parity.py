@@ -1437,7 +1437,7 @@ def test_encoder_layer_executor_vs_torch_and_per_op_path(G, b, hch, fch, t, nl, 
 @pytest.mark.usefixtures("conv_mode")
 @pytest.mark.parametrize("b,h,t,blocks,p_drop,sig,gin", [(3, 192, 100, 2, 0.0, False, 0), (2, 192, 64, 2, 0.05, False, 0),
                                                            (2, 48, 37, 3, 0.0, True, 0), (3, 192, 80, 2, 0.05, False, 16),
-                                                           (2, 48, 37, 2, 0.0, True, 8)])
+                                                           (2, 48, 37, 2, 0.0, True, 8), (2, 48, 37, 1, 0.0, True, 0)])
 def test_flow_block_executor_matches_per_op_path(G, b, h, t, blocks, p_drop, sig, gin):
     """convops.FlowBlockFn (a whole [ActNorm, InvConvNear, CouplingBlock] block queued from C, one autograd node) against
     the per-operator path (five nodes per block): same kernels in the same order, so outputs agree to rounding of the
@@ -1502,6 +1502,8 @@ def test_flow_block_executor_matches_per_op_path(G, b, h, t, blocks, p_drop, sig
     if gin == 0:                                         # the two half-batch chains run the same kernels on the same utterances
         assert torch.equal(res["stack+half"][0], res["stack"][0])            # (the log-determinants are sums of float atomics)
         assert_close(res["stack+half"][1], res["stack"][1], what="stack+half: logdet", rtol=1e-6, atol=1e-4)
+    if blocks == 1:                                      # a one-block stack makes neither the fused launch nor the stack pack: it
+        assert torch.equal(res["stack"][0], res["both"][0])                  # queues the launches of the per-block node
     z0, l0, dx0, g0 = res["fwd"]
     for mode in ("both", "stack", "stack+bwd", "stack+half"):
         z1, l1, dx1, g1 = res[mode]

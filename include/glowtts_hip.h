@@ -290,12 +290,16 @@ int glowtts_res_skip_bwd(const float *dx_out, const float *dskip, const float *m
  * `*_bs` = batch stride in elements (lets a channel slice such as x[:, :C/2] be consumed in place).
  * Packed weights ("k-packed": 16 consecutive reduction channels per 64-byte row, zero beyond the channel count):
  *   wp_f[tap][ceil(Cin/16)][Cout][16] (forward) and wp_b[taps-1-tap][ceil(Cout/16)][Cin][16] (backward-data), produced by
- * glowtts_pack_weight, which also applies torch's weight_norm (w = g v / ||v||, dim 0) when g != NULL.  The weight
+ * glowtts_pack_weight, which also applies torch's weight_norm (w = g v / ||v||, dim 0) when g != NULL.  pack_weight
+ * writes the slots of existing channels only: where a channel count is no multiple of 16 the CALLER zero-fills the packed
+ * buffer first (the kernels multiply those slots with zeros, which a NaN would survive).  The weight
  * gradient (conv_wrw) is produced in the plain [tap][Cin][Cout] order that unpack_weight_grad consumes.
  *
  * conv_fwd      : y[b,m,t] = sum_tap sum_k wp[tap][k][m] * (x[b,k,t + tap*dil - pad] * (mask_in ? mask : 1)) + bias[m]
- *                 then (* mask if mask_out) ; if addend != NULL: y += addend (* mask if mask_add)
- *                 (backward-data = the same call with wp_b, Cin/M swapped, pad' = (taps-1)*dil - pad)
+ *                 then, if addend != NULL: y += addend (* mask if mask_add) ; then (* mask if mask_out): the mask covers
+ *                 the sum, as in `(conv(x) + residual) * mask`
+ *                 (any pad >= 0: y has T frames, frames outside [0, T) read as 0;
+ *                 backward-data = the same call with wp_b, Cin/M swapped, pad' = (taps-1)*dil - pad)
  * conv_gate_fwd : WN in-layer + gate: pre = conv(x) + bias, dropout keep-mask bytes `drop` (scale 1/(1-p)) applied to
  *                 pre, + cond[b, :] ; acts = tanh(pre[:H]) * sigmoid(pre[H:]) ; ts (B,2H,T) = the tanh / sigmoid values
  * conv_res_skip_fwd : WN res/skip 1x1 + update: rs = W acts + b ; x_out = (x_in + rs[:H]) * mask ; skip_out = skip_in + rs[H:]

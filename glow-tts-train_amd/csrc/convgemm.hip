@@ -22,10 +22,9 @@
 //     dWp[tap][k][m] += sum_{b,t} X[b][k][t + tap*dil - pad] * D[b][m][t]
 //   A = X rows (k), B = D rows (m), contraction over time; split over utterance groups, one float atomic per
 //   element and workgroup (64-B contiguous segments along m).
-#include "convgemm_common.hpp"
+#include "conv_plan.hpp"
 
 namespace glowtts {
-
 
 // ------------------------------------------------------------------------------------------------------------
 // Forward-type kernel history (profiles/, tools/mfma_rate.hip, tools/trace_conv.py):
@@ -291,8 +290,6 @@ __global__ __launch_bounds__(256) void convwrw_kernel(ConvWrwParams p) {
 // software-pipelined weight gradient: workgroup = 64 input channels (one 16-row k-tile per wave) x 64 output channels
 // (4 m-tiles per wave) x ALL taps (each tap is the same staged X slab read at a shifted column), contraction over the
 // frames of `nb` utterances in chunks of CT frames; chunk c+1 travels HBM/L2 -> registers while chunk c feeds the MFMAs.
-constexpr int cpitch2(int n) { return ((n - 2 + 31) / 32 * 32 + 2) < n ? ((n - 2 + 31) / 32 * 32 + 2) + 32 : ((n - 2 + 31) / 32 * 32 + 2); }
-
 template <int TAPS, int CT>
 __global__ __launch_bounds__(256) void convwrw_pipe_kernel(ConvWrwParams p) {
     constexpr int XC = CT + 16;
@@ -489,8 +486,6 @@ __global__ __launch_bounds__(256) void convwrw_pipe_kernel(ConvWrwParams p) {
 //   store is the 16-byte load written back as one ds_write_b128.
 // One LDS image; chunk c+1 waits in registers behind the MFMAs of chunk c.  Masks go through a small LDS window.
 // ------------------------------------------------------------------------------------------------------------
-__host__ __device__ constexpr int cpitch4(int w) { int p = (w + 3) / 4 * 4; while (p % 8 != 4) p += 4; return p; }
-
 template <int TAPS, int NGRP, int MT>      // MT = 16-row output-gradient tiles per wave: workgroup tile 64 k x 16*MT m
 __global__ __launch_bounds__(256, (MT <= 2 ? 3 : 2)) void convwrw_fp_kernel(ConvWrwParams p) {
     constexpr int MR = 16 * MT;
@@ -822,151 +817,230 @@ __global__ __launch_bounds__(256) void rowsum_kernel(const float *__restrict__ d
     if (threadIdx.x == 0) atomicAdd(out + m, s);
 }
 
-static inline int pitch16(int n) {          // smallest pitch >= n with pitch % 32 == 16
-    int p = (n + 15) / 32 * 32 + 16;
-    if (p - 32 >= n) p -= 32;
-    return p;
-}
+// ------------------------------------------------------------------------------------------------------------
+// host side: plan (conv_plan.hpp has the rules), then launch
+// ------------------------------------------------------------------------------------------------------------
+thread_local ConvPlan *t_conv_plan_out = nullptr;
+
 static inline int pitch2(int n) {           // smallest pitch >= n with pitch % 32 == 2
     int p = (n - 2 + 31) / 32 * 32 + 2;
     return p < n ? p + 32 : p;
 }
 
-template <int RTW, int NCT, int EPI>
-static int launch_convgemm(ConvGemmParams &p, hipStream_t s) {
-    constexpr int WGR = 64 * RTW, NT = 16 * NCT;
-    p.xp_pitch = pitch16(NT + (p.taps - 1) * p.dil);
-    const size_t lds = ((size_t)p.taps * 16 * (WGR + 16) + (size_t)16 * p.xp_pitch) * sizeof(float);
-    GLOWTTS_CHECK_ARG(lds <= 160 * 1024, "glowtts_conv: %d taps x dilation %d needs %zu B of LDS", p.taps, p.dil, lds);
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convgemm_kernel<RTW, NCT, EPI>), lds, "glowtts_conv")) return rc_;
-    const int ntile_t = (p.T + NT - 1) / NT;
-    const int rows = (EPI == EPI_GATE) ? p.H : p.M;
-    const int per = (EPI == EPI_GATE) ? 64 : WGR;
-    dim3 grid(ntile_t * p.B, (rows + per - 1) / per);
-    hipLaunchKernelGGL((convgemm_kernel<RTW, NCT, EPI>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv");
-}
-
-template <int RTW, int NCT, int EPI, int TAPS>
-static int launch_convgemm_wd(ConvGemmParams &p, hipStream_t s) {
-    constexpr int WGR = 64 * RTW, NT = 16 * NCT;
-    constexpr size_t lds_pipe = ((size_t)6 * (NT + 16) * 20 + (NT + 16)) * sizeof(float);
-    constexpr size_t lds_epi = ((size_t)WGR * (NT + 4) + (EPI == EPI_GATEBWD ? 2 * WGR : 0)) * sizeof(float);
-    constexpr size_t lds = lds_pipe > lds_epi ? lds_pipe : lds_epi;
-    static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    p.vec_epilogue = aligned16(p.y0) && aligned16(p.y1) && aligned16(p.r0) && aligned16(p.r1) && aligned16(p.mask) &&
-                     aligned16(p.drop) && aligned16(p.gate_pos) && (p.y_bs % 4 == 0) && (p.r_bs % 4 == 0) &&
-                     (EPI != EPI_GATE || p.H % 4 == 0);
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convgemm_wd_kernel<RTW, NCT, EPI, TAPS>), lds, "glowtts_conv")) return rc_;
-    const int ntile_t = (p.T + NT - 1) / NT;
-    const int rows = (EPI == EPI_GATE) ? p.H : p.M;
-    const int per = (EPI == EPI_GATE) ? 64 : WGR;
-    dim3 grid(ntile_t * p.B, (rows + per - 1) / per);
-    hipLaunchKernelGGL((convgemm_wd_kernel<RTW, NCT, EPI, TAPS>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv");
-}
-
-template <int RTW, int NCT, int EPI>
-static int dispatch_taps(ConvGemmParams &p, hipStream_t s, bool pipe_ok) {
-    if (pipe_ok) {
-        if (p.taps == 5) return launch_convgemm_wd<RTW, NCT, EPI, 5>(p, s);
-        if (p.taps == 3) return launch_convgemm_wd<RTW, NCT, EPI, 3>(p, s);
-        if (p.taps == 1) return launch_convgemm_wd<RTW, NCT, EPI, 1>(p, s);
+// How a forward-type launch is chosen: the Winograd forms where their U planes are bound; bf16 tensors on the one kernel family that
+// reads them (an error where it has no form for the shape); then 32 / 64 / 80-frame tiles and 64 / 128 rows, on the bf16-plane
+// kernel where the mode is on, planes are bound and the form exists, else on the fp32 MFMA: pipelined for 1 / 3 / 5 taps on 16-byte
+// rows, generic for everything else.
+int plan_conv_fwd(const ConvGemmParams &p, int epi, const ConvSnapshot &sn, ConvPlan &plan) {
+    plan = ConvPlan{};
+    plan.epi = epi; plan.block = 256; plan.launches = 1;
+    if (epi == EPI_GATE && plan_wino_gate(p, sn, plan)) return 0;
+    if ((epi == EPI_PLAIN || epi == EPI_ADD) && plan_wino_bwd(p, sn, plan)) return 0;
+    const bool n5 = frames80_fwd(p.T), big = rows_big(epi, p.M), pipe_ok = fwd_pipe_ok(p, epi);
+    if (p.xb) {                                       // bf16 tensors in HBM: there is no fp32 kernel that could read them
+        GLOWTTS_CHECK_ARG(pipe_ok && (p.T % 4) == 0, "glowtts_conv (bf16 tensors): needs T %% 4 == 0 and 16-byte aligned rows");
+        GLOWTTS_CHECK_ARG(sn.bound_ns == 3, "glowtts_conv (bf16 tensors): the packed weights have no bf16 planes bound "
+                          "(glowtts_split_planes(wp, n, planes, 3) + glowtts_conv_bind_planes_ns(wp, n, planes, 3))");
+        // the 1x1 PLAIN / ADD convolutions (start, end, start's input gradient) exist with 64-row workgroups only, which serve
+        // any M: the 128-row preference (M % 128 == 0 or M > 192: squeezed C = 128 / 256) must not leave them without a kernel
+        plan.rows = (big && !(p.taps == 1 && (epi == EPI_PLAIN || epi == EPI_ADD))) ? 128 : 64;
+        plan.iob = p.yb ? 1 : 2;
+        GLOWTTS_CHECK_ARG(conv_bf16_has(plan.iob, epi, plan.rows, p.taps), "glowtts_conv (bf16 tensors): no kernel for epilogue %d, taps %d, M %d, output %s",
+                          epi, p.taps, p.M, p.yb ? "bf16" : "fp32");
+        plan.family = GLOWTTS_PLAN_BF16IO;
+        plan.ns = 1; plan.nsa = plan.iob == 2 ? 3 : 1;     // fp32 results: the exact weights, three planes
+        plan.frame_tile = n5 ? 80 : 64;
+    } else {
+        plan.frame_tile = fwd_use32(p, epi, big, pipe_ok, sn.knob[K_CONV32_1X1]) ? 32 : (n5 ? 80 : 64);
+        plan.rows = big ? 128 : 64;
+        if (sn.math_fwd != 0 && pipe_ok && sn.bound_ns == sn.math_fwd && conv_split_has(sn.math_fwd, epi, plan.rows, p.taps, plan.frame_tile)) {
+            plan.family = GLOWTTS_PLAN_SPLIT;
+            plan.ns = plan.nsa = sn.math_fwd;
+        }
     }
-    return launch_convgemm<RTW, NCT, EPI>(p, s);
+    fwd_grid(p, plan);
+    if (plan.family != GLOWTTS_PLAN_NONE) {           // the bf16 matrix pipe, either way
+        plan.taps = p.taps;
+        plan.vec_epilogue = vec_epilogue(p, epi, false);
+        plan.wg_order = (plan.grid_y > 1 && plan.grid_x % 8 == 0 && sn.knob[K_CONV_ROW_ADJ] == 1) ? 1 : 0;
+        plan.lds_bytes = (int)lds_conv_split(plan.ns, plan.rows, plan.frame_tile, epi);
+    } else if (pipe_ok && (p.taps == 1 || p.taps == 3 || p.taps == 5)) {
+        plan.family = GLOWTTS_PLAN_PIPE;
+        plan.taps = p.taps;
+        plan.vec_epilogue = vec_epilogue(p, epi, true);
+        plan.lds_bytes = (int)lds_conv_pipe(plan.rows, plan.frame_tile, epi);
+    } else {
+        plan.family = GLOWTTS_PLAN_GENERIC;
+        plan.xp_pitch = pitch16(plan.frame_tile + (p.taps - 1) * p.dil);
+        const size_t lds = ((size_t)p.taps * 16 * (plan.rows + 16) + (size_t)16 * plan.xp_pitch) * sizeof(float);
+        GLOWTTS_CHECK_ARG(lds <= 160 * 1024, "glowtts_conv: %d taps x dilation %d needs %zu B of LDS", p.taps, p.dil, lds);
+        plan.lds_bytes = (int)lds;
+    }
+    return 0;
 }
 
+// the ladder of the fp32 MFMA forward-type kernels: epilogue, rows and frame tile, then generic or pipelined by taps
+template <int RTW, int NCT, int EPI>
+static int launch_native_tile(const ConvGemmParams &p, const ConvPlan &plan, hipStream_t s) {
+    static_assert(lds_conv_pipe(64 * RTW, 16 * NCT, EPI) <= 80 * 1024, "two workgroups per CU");
+    if (plan.family == GLOWTTS_PLAN_GENERIC) return launch_planned<&convgemm_kernel<RTW, NCT, EPI>>(plan, "glowtts_conv", s, p);
+    if (plan.taps == 5) return launch_planned<&convgemm_wd_kernel<RTW, NCT, EPI, 5>>(plan, "glowtts_conv", s, p);
+    if (plan.taps == 3) return launch_planned<&convgemm_wd_kernel<RTW, NCT, EPI, 3>>(plan, "glowtts_conv", s, p);
+    return launch_planned<&convgemm_wd_kernel<RTW, NCT, EPI, 1>>(plan, "glowtts_conv", s, p);
+}
 template <int EPI>
-static int dispatch_convgemm(ConvGemmParams &p, hipStream_t s) {
-    // 80-frame tiles when T divides evenly (e.g. T' = 400), else 64; 128-row workgroups unless M is small
-    const bool n5 = (p.T % 80 == 0) || (p.T % 64 != 0 && ((p.T + 79) / 80) * 80 < ((p.T + 63) / 64) * 64);
-    const bool big = (EPI == EPI_GATE) || (p.M % 128 == 0) || p.M > 192;
-    const bool pipe_ok = (p.T % 4 == 0) && aligned16(p.x) && (p.x_bs % 4 == 0) &&
-                         (!p.mask_in || aligned16(p.mask)) && ((p.taps - 1) * p.dil <= 12) &&
-                         (EPI != EPI_GATE || p.H % 4 == 0);
-    if (p.xb) return conv_bf16_dispatch(p, EPI, big, n5, pipe_ok, s);                     // bf16 tensors in HBM
-    // Small problems (the text encoder: T = 160) give only ~190 workgroups with 80-frame tiles — less than one per CU.
-    // 32-frame tiles fill the chip (480+ workgroups): -15..20 % on the encoder's 3-tap and 1-tap convs.  At the decoder's
-    // T' = 400 (480 workgroups already) the smaller tiles only lose operand reuse, so the switch is on the grid size.
-    bool use32 = false;
-    if constexpr (EPI == EPI_PLAIN) if (pipe_ok) {
-        const int rows_per = big ? 128 : 64;
-        const long wg5 = (long)((p.T + 79) / 80) * p.B * ((p.M + rows_per - 1) / rows_per);
-        const int t32 = ((p.T + 31) / 32) * 32;
-        // (threshold 440 -> 380 in round 4: the FFN's 768 <- 192-channel 3-tap convolutions at T = 160 have 384 tiles of 128 rows
-        // x 80 frames, which the bf16-plane kernel runs in 80-frame form — its 32-frame 128-row form does not exist, and the native
-        // 32-frame kernel that served them took 49 us: 15.00 -> 14.81 ms per step, tools/ab_flags.py envs=GLOWTTS_CONV32_WG:440,..:380;
-        // 190 and 0 measured 14.87 / 14.96 against 14.90)
-        use32 = wg5 < 380 && t32 * 10 <= p.T * 11;
-        // plain 1x1 convolutions (the coupling's start / end convs and the end conv's backward-data: 12 800 columns, 480 tiles of
-        // 80 frames) take 32-frame tiles as well: four consecutive A/B pairs 15.04 -> 15.00 ms per step (GLOWTTS_CONV32_1X1=0 / 1)
-        if (p.taps == 1 && t32 * 10 <= p.T * 11 && knob(K_CONV32_1X1) == 1) use32 = true;
+static int launch_native_epi(const ConvGemmParams &p, const ConvPlan &plan, hipStream_t s) {
+    const bool big = plan.rows == 128;
+    if (plan.frame_tile == 32) return big ? launch_native_tile<2, 2, EPI>(p, plan, s) : launch_native_tile<1, 2, EPI>(p, plan, s);
+    if (plan.frame_tile == 80) return big ? launch_native_tile<2, 5, EPI>(p, plan, s) : launch_native_tile<1, 5, EPI>(p, plan, s);
+    return big ? launch_native_tile<2, 4, EPI>(p, plan, s) : launch_native_tile<1, 4, EPI>(p, plan, s);
+}
+static int launch_conv_native(ConvGemmParams &p, const ConvPlan &plan, hipStream_t s) {
+    p.xp_pitch = plan.xp_pitch;
+    p.vec_epilogue = plan.vec_epilogue;
+    switch (plan.epi) {
+    case EPI_GATE: return launch_native_epi<EPI_GATE>(p, plan, s);
+    case EPI_RESSKIP: return launch_native_epi<EPI_RESSKIP>(p, plan, s);
+    case EPI_RESSKIP_LAST: return launch_native_epi<EPI_RESSKIP_LAST>(p, plan, s);
+    case EPI_ADD: return launch_native_epi<EPI_ADD>(p, plan, s);
+    case EPI_GATEBWD: return launch_native_epi<EPI_GATEBWD>(p, plan, s);
+    default: return launch_native_epi<EPI_PLAIN>(p, plan, s);
     }
-    if (int rc = conv_split_dispatch(p, EPI, big, use32 ? 2 : (n5 ? 5 : 4), pipe_ok, s); rc >= 0) return rc;   // bf16-plane arithmetic
-    if (use32) {
-        if (big) return dispatch_taps<2, 2, EPI>(p, s, pipe_ok);
-        return dispatch_taps<1, 2, EPI>(p, s, pipe_ok);
-    }
-    if (EPI == EPI_GATE) return n5 ? dispatch_taps<2, 5, EPI>(p, s, pipe_ok) : dispatch_taps<2, 4, EPI>(p, s, pipe_ok);
-    if (big) return n5 ? dispatch_taps<2, 5, EPI>(p, s, pipe_ok) : dispatch_taps<2, 4, EPI>(p, s, pipe_ok);
-    return n5 ? dispatch_taps<1, 5, EPI>(p, s, pipe_ok) : dispatch_taps<1, 4, EPI>(p, s, pipe_ok);
 }
 
-template <int TAPS, int NGRP, int MT>
-static int launch_wrw_fp_mt(ConvWrwParams &p, hipStream_t s) {
-    constexpr int CT = 16 * NGRP, MR = 16 * MT;
-    constexpr size_t lds = ((size_t)64 * cpitch4(CT + 16) + (size_t)MR * cpitch4(CT) + (CT + 16) + CT) * sizeof(float);
-    static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convwrw_fp_kernel<TAPS, NGRP, MT>), lds, "glowtts_conv_wrw")) return rc_;
-    // all workgroups resident at once (2 per CU: 512 slots); p.nb = chunks of CT frames per workgroup
-    const int tiles = ((p.Cin + 63) / 64) * ((p.M + MR - 1) / MR);
-    const int total = p.B * ((p.T + CT - 1) / CT);
-    int splits = (MT <= 2 ? 768 : 512) / tiles;
-    if (splits > total) splits = total;
-    if (splits < 1) splits = 1;
-    p.nb = (total + splits - 1) / splits;
-    dim3 grid(tiles, 1, (total + p.nb - 1) / p.nb);
-    hipLaunchKernelGGL((convwrw_fp_kernel<TAPS, NGRP, MT>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw");
+static int launch_conv_fwd(ConvGemmParams &p, const ConvPlan &plan, const ConvSnapshot &sn, hipStream_t s) {
+    switch (plan.family) {
+    case GLOWTTS_PLAN_WINO_GATE: return launch_wino_gate(p, plan, sn, s);
+    case GLOWTTS_PLAN_WINO_BWD: return launch_wino_bwd(p, plan, sn, s);
+    case GLOWTTS_PLAN_SPLIT:
+    case GLOWTTS_PLAN_BF16IO: return launch_conv_split(p, plan, sn, s);
+    default: return launch_conv_native(p, plan, s);
+    }
 }
 
-template <int TAPS, int NGRP>
-static int launch_wrw_fp(ConvWrwParams &p, hipStream_t s) {
-    // 5 taps: 64 k x 32 m tiles — 40 accumulator registers per lane instead of 80, so THREE workgroups fit a CU (168
-    // VGPRs, 36 KB LDS) and hide each other's prologue / atomics epilogue: 107 -> 96 us at config 2.  With 3 taps or 1 the
-    // 64 x 64 tile already leaves room for three, and the smaller tile only costs operand reuse.
+// what every forward-type entry point ends in.  wino: glowtts_conv_fwd_act has never taken the Winograd forms.
+static int conv_fwd_go(ConvGemmParams &p, int epi, bool wino, hipStream_t s) {
+    ConvSnapshot sn = conv_snapshot(p.wp, wino, false);
+    ConvPlan plan;
+    if (int rc = plan_conv_fwd(p, epi, sn, plan)) return rc;
+    if (ConvPlan *out = conv_plan_take()) { *out = plan; return 0; }
+    int rc = launch_conv_fwd(p, plan, sn, s);
+    if (rc == -1) {      // the Winograd backward-data has no workspace on this stream yet and the stream is being captured (or the
+        sn.wino_u = nullptr;                          // allocation failed): the direct plan, decided here because only the launch can know
+        if (int rc2 = plan_conv_fwd(p, epi, sn, plan)) return rc2;
+        rc = launch_conv_fwd(p, plan, sn, s);
+    }
+    return rc;
+}
+
+// workgroups resident at once with two / three per CU: what the weight gradients size their split-K for
+constexpr int kSlots2 = 512, kSlots3 = 768;
+
+// How a weight-gradient launch is chosen: operands given as planes on their own kernel (an error where it has no form); 1 / 3 / 5
+// taps at dilation 1 with 'same' padding on 16-byte rows are frame-packed — in a plane mode on the transposed-read kernel (5 and 3
+// taps) or the bf16-plane kernel (5 taps with 32-row tiles, 1 tap), else on the fp32 MFMA; other dilations / paddings on the
+// pipelined kernel; everything else on the generic one, whose bias gradient is a second launch.  Only the plane kernels take a
+// batch (p.nbatch > 1): GLOWTTS_PLAN_NONE tells glowtts_conv_wrw_batch to go problem by problem.
+int plan_conv_wrw(const ConvWrwParams &p, int planes_ns, const ConvSnapshot &sn, ConvPlan &plan) {
+    plan = ConvPlan{};
+    plan.block = 256; plan.launches = 1; plan.rows = 64; plan.nbatch = p.nbatch; plan.taps = p.taps;
+    const int tiles64 = (p.Cin + 63) / 64, ct = frames80_wrw(p.T) ? 80 : 64, mt = wrw_fp_mt(p);
+    auto frame_packed = [&](int family, int ns, size_t lds, int slots) {
+        plan.family = family; plan.ns = plan.nsa = ns; plan.mt = mt; plan.frame_tile = ct;
+        plan.lds_bytes = (int)lds;
+        const int tiles = tiles64 * ((p.M + 16 * mt - 1) / (16 * mt));
+        wrw_split_k(plan, tiles, p.B * ((p.T + ct - 1) / ct), slots / tiles);
+    };
+    if (p.xpl) {                                      // one plane = the tensors ARE bf16 (flow blocks with bf16 activations in HBM)
+        GLOWTTS_CHECK_ARG((planes_ns == 3 || planes_ns == 1) && ((p.taps == 5 && p.M % 32 == 0) || p.taps == 1),
+                          "glowtts_conv_wrw_planes: no kernel for taps=%d, M=%d, planes=%d (3 planes; 5 taps with M %% 32 == 0, or 1 tap)",
+                          p.taps, p.M, planes_ns);
+        frame_packed(GLOWTTS_PLAN_WRW_PLANES, planes_ns, lds_wrw_split(planes_ns, ct, 16 * mt), kSlots2);
+        return 0;
+    }
+    if (wrw_frame_packed(p)) {
+        const int ns = sn.math_wrw;
+        if (ns != 0 && plan_wrw_tr(p, sn, plan)) return 0;
+        // (all workgroups resident at once, 2 per CU; 256 / 128 slots for the single launches measured 15.08 / 15.17 ms per step
+        // against 15.11: no gain)
+        if (ns != 0 && ((p.taps == 5 && mt == 2) || p.taps == 1)) frame_packed(GLOWTTS_PLAN_WRW_SPLIT, ns, lds_wrw_split(ns, ct, 16 * mt), kSlots2);
+        else if (p.nbatch <= 1) frame_packed(GLOWTTS_PLAN_WRW_FP, 0, lds_wrw_fp(ct, 16 * mt), mt <= 2 ? kSlots3 : kSlots2);
+        return 0;
+    }
+    if (p.nbatch > 1) return 0;
+    if (wrw_pipe_ok(p) && (p.taps == 1 || p.taps == 3 || p.taps == 5)) {
+        plan.family = GLOWTTS_PLAN_WRW_PIPE;
+        plan.mt = 4;
+        plan.frame_tile = (p.T % 40 == 0) ? 40 : 32;
+        plan.lds_bytes = (int)lds_wrw_pipe(plan.frame_tile);
+        const int tiles = tiles64 * ((p.M + 63) / 64);
+        wrw_split_k(plan, tiles, p.B * ((p.T + plan.frame_tile - 1) / plan.frame_tile), kSlots2 / tiles);
+        return 0;
+    }
+    plan.family = GLOWTTS_PLAN_WRW_GENERIC;
+    plan.taps = 0; plan.mt = 8; plan.frame_tile = 64;
+    plan.xp_pitch = pitch2(64);
+    plan.lds_bytes = (int)(((size_t)64 * plan.xp_pitch + (size_t)128 * plan.xp_pitch) * sizeof(float));
+    const int tiles = tiles64 * ((p.M + 127) / 128);
+    wrw_split_k(plan, tiles, p.B, (kSlots3 + tiles * p.taps - 1) / (tiles * p.taps));     // utterances per workgroup; aim at ~3 workgroups per CU
+    plan.grid_y = p.taps;
+    plan.launches = p.dbias ? 2 : 1;                  // the row sums of d: glowtts_rowsum
+    return 0;
+}
+
+extern "C" int glowtts_rowsum(const float *d, long d_bs, const float *mask, float *out, int B, int M, int T,
+                              glowtts_stream_t stream);
+
+// the ladder of the fp32 MFMA weight-gradient kernels
+template <int TAPS>
+static int launch_wrw_native_taps(const ConvWrwParams &p, const ConvPlan &plan, hipStream_t s) {
+    static_assert(lds_wrw_fp(80, 64) <= 80 * 1024, "two workgroups per CU");
+    const bool n5 = plan.frame_tile == 80;
+    if (plan.family == GLOWTTS_PLAN_WRW_PIPE)
+        return plan.frame_tile == 40 ? launch_planned<&convwrw_pipe_kernel<TAPS, 40>>(plan, "glowtts_conv_wrw", s, p)
+                                     : launch_planned<&convwrw_pipe_kernel<TAPS, 32>>(plan, "glowtts_conv_wrw", s, p);
     if constexpr (TAPS == 5)
-        if (p.M % 32 == 0 && (!p.d2 || p.d_split % 32 == 0)) return launch_wrw_fp_mt<TAPS, NGRP, 2>(p, s);
-    return launch_wrw_fp_mt<TAPS, NGRP, 4>(p, s);
+        if (plan.mt == 2)
+            return n5 ? launch_planned<&convwrw_fp_kernel<5, 5, 2>>(plan, "glowtts_conv_wrw", s, p)
+                      : launch_planned<&convwrw_fp_kernel<5, 4, 2>>(plan, "glowtts_conv_wrw", s, p);
+    return n5 ? launch_planned<&convwrw_fp_kernel<TAPS, 5, 4>>(plan, "glowtts_conv_wrw", s, p)
+              : launch_planned<&convwrw_fp_kernel<TAPS, 4, 4>>(plan, "glowtts_conv_wrw", s, p);
 }
 
-template <int TAPS, int CT>
-static int launch_wrw_pipe(ConvWrwParams &p, hipStream_t s) {
-    constexpr size_t lds = 2 * ((size_t)64 * cpitch2(CT + 16) + (size_t)64 * cpitch2(CT)) * sizeof(float);
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convwrw_pipe_kernel<TAPS, CT>), lds, "glowtts_conv_wrw")) return rc_;
-    // The contraction runs over B * T frames = `total` chunks of CT; it is split so that ALL workgroups are resident at
-    // once (2 per CU by LDS, 512 slots): a grid of 576 on 512 slots costs two full rounds.  p.nb = chunks per workgroup.
-    const int tiles = ((p.Cin + 63) / 64) * ((p.M + 63) / 64);
-    const int total = p.B * ((p.T + CT - 1) / CT);
-    int splits = 512 / tiles;
-    if (splits > total) splits = total;
-    if (splits < 1) splits = 1;
-    p.nb = (total + splits - 1) / splits;
-    dim3 grid(tiles, 1, (total + p.nb - 1) / p.nb);
-    hipLaunchKernelGGL((convwrw_pipe_kernel<TAPS, CT>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw");
+static int launch_conv_wrw(ConvWrwParams &p, const ConvPlan &plan, hipStream_t s) {
+    p.nb = plan.nb;
+    switch (plan.family) {
+    case GLOWTTS_PLAN_WRW_TR: return launch_wrw_tr(p, plan, s);
+    case GLOWTTS_PLAN_WRW_SPLIT:
+    case GLOWTTS_PLAN_WRW_PLANES: return launch_wrw_split(p, plan, s);
+    case GLOWTTS_PLAN_WRW_GENERIC: {
+        p.xs_pitch = p.ds_pitch = plan.xp_pitch;
+        const int rc = launch_planned<&convwrw_kernel>(plan, "glowtts_conv_wrw", s, p);
+        return (rc == 0 && p.dbias) ? glowtts_rowsum(p.d, p.d_bs, p.mask, p.dbias, p.B, p.M, p.T, s) : rc;
+    }
+    default: break;
+    }
+    if (plan.taps == 5) return launch_wrw_native_taps<5>(p, plan, s);
+    if (plan.taps == 3) return launch_wrw_native_taps<3>(p, plan, s);
+    return launch_wrw_native_taps<1>(p, plan, s);
+}
+
+int conv_wrw_go(ConvWrwParams &p, int planes_ns, hipStream_t s, ConvPlan *dry) {
+    ConvPlan plan;
+    if (int rc = plan_conv_wrw(p, planes_ns, conv_snapshot(nullptr, false, true), plan)) return rc;
+    if (plan.family == GLOWTTS_PLAN_NONE) return -1;
+    if (dry) {
+        const int before = dry->launches;
+        if (dry->family == GLOWTTS_PLAN_NONE) *dry = plan;
+        dry->launches = before + plan.launches;
+        return 0;
+    }
+    return launch_conv_wrw(p, plan, s);
 }
 
 }  // namespace glowtts
 
 using namespace glowtts;
-
-extern "C" int glowtts_rowsum(const float *d, long d_bs, const float *mask, float *out, int B, int M, int T,
-                              glowtts_stream_t stream);
 
 static int check_conv_common(const char *name, const void *x, const void *wp, int B, int Cin, int M, int T, int taps,
                              int dil, int pad) {
@@ -974,6 +1048,11 @@ static int check_conv_common(const char *name, const void *x, const void *wp, in
     GLOWTTS_CHECK_ARG(B >= 0 && Cin > 0 && M > 0 && T >= 0 && taps >= 1 && dil >= 1 && pad >= 0,
                       "%s: bad shape B=%d Cin=%d M=%d T=%d taps=%d dil=%d pad=%d", name, B, Cin, M, T, taps, dil, pad);
     GLOWTTS_CHECK_ARG(aligned16(wp), "%s: packed weights must be 16-byte aligned", name);
+    return 0;
+}
+
+extern "C" int glowtts_conv_plan_next(glowtts_conv_plan *out) {
+    t_conv_plan_out = out;
     return 0;
 }
 
@@ -993,11 +1072,7 @@ extern "C" int glowtts_conv_fwd_io(const void *x, long x_bs, const float *wp, co
     p.y0 = static_cast<float *>(y); p.xb = io_x; p.yb = io_y;
     p.x_bs = x_bs; p.y_bs = y_bs; p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
     p.mask_in = mask_in; p.mask_out = mask_out; p.mask_add = mask_add; p.r_bs = addend_bs;
-    if (io_x == 0 && io_y == 0) {                    // the gated in-conv's backward-data in Winograd form where its U planes are bound
-        const int rc = conv_wino_bwd_dispatch(p, (hipStream_t)stream);
-        if (rc >= 0) return rc;
-    }
-    return addend ? dispatch_convgemm<EPI_ADD>(p, (hipStream_t)stream) : dispatch_convgemm<EPI_PLAIN>(p, (hipStream_t)stream);
+    return conv_fwd_go(p, addend ? EPI_ADD : EPI_PLAIN, true, (hipStream_t)stream);
 }
 
 // conv_fwd with the elementwise neighbours of the text encoder's convolutions folded into the epilogue (fp32 tensors):
@@ -1019,7 +1094,7 @@ extern "C" int glowtts_conv_fwd_act(const float *x, long x_bs, const float *wp, 
     p.x_bs = x_bs; p.y_bs = y_bs; p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
     p.mask_in = mask_in; p.mask_out = mask_out; p.mask_add = mask_add; p.r_bs = addend_bs;
     p.relu = relu; p.drop = drop; p.drop_scale = drop_scale; p.gate_pos = gate_pos; p.gate_scale = gate_scale;
-    return addend ? dispatch_convgemm<EPI_ADD>(p, (hipStream_t)stream) : dispatch_convgemm<EPI_PLAIN>(p, (hipStream_t)stream);
+    return conv_fwd_go(p, addend ? EPI_ADD : EPI_PLAIN, false, (hipStream_t)stream);
 }
 
 extern "C" int glowtts_conv_fwd(const float *x, long x_bs, const float *wp, const float *bias, const float *mask,
@@ -1041,11 +1116,7 @@ extern "C" int glowtts_conv_gate_fwd_io(const void *x, const float *wp, const fl
     p.x = static_cast<const float *>(x); p.wp = wp; p.bias = bias; p.cond = cond; p.drop = drop; p.drop_scale = drop_scale;
     p.y0 = static_cast<float *>(acts); p.y1 = static_cast<float *>(ts); p.xb = io; p.yb = io;
     p.x_bs = (long)H * T; p.B = B; p.Cin = H; p.M = 2 * H; p.H = H; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
-    if (io == 0) {                                   // Winograd form where U planes are bound and the switch is on (convwino.hip)
-        const int rc = conv_wino_gate_dispatch(p, (hipStream_t)stream);
-        if (rc >= 0) return rc;
-    }
-    return dispatch_convgemm<EPI_GATE>(p, (hipStream_t)stream);
+    return conv_fwd_go(p, EPI_GATE, true, (hipStream_t)stream);
 }
 
 extern "C" int glowtts_conv_gate_fwd(const float *x, const float *wp, const float *bias, const float *cond,
@@ -1066,8 +1137,7 @@ extern "C" int glowtts_conv_res_skip_fwd_io(const void *acts, const float *wp, c
     p.r1 = static_cast<const float *>(skip_in); p.y0 = static_cast<float *>(x_out); p.y1 = static_cast<float *>(skip_out);
     p.xb = io; p.yb = io;
     p.x_bs = (long)H * T; p.B = B; p.Cin = H; p.M = M; p.H = H; p.T = T; p.taps = 1; p.dil = 1; p.pad = 0;
-    return last ? dispatch_convgemm<EPI_RESSKIP_LAST>(p, (hipStream_t)stream)
-                : dispatch_convgemm<EPI_RESSKIP>(p, (hipStream_t)stream);
+    return conv_fwd_go(p, last ? EPI_RESSKIP_LAST : EPI_RESSKIP, true, (hipStream_t)stream);
 }
 
 extern "C" int glowtts_conv_res_skip_fwd(const float *acts, const float *wp, const float *bias, const float *mask,
@@ -1092,7 +1162,7 @@ extern "C" int glowtts_conv_gate_bwd_io(const void *d_rs, const void *d_rs2, con
                           "glowtts_conv_gate_bwd: two-source input needs M_rs == 2H, H %% 96 == 0, T %% 4 == 0, 16-byte rows");
         p.x_bs = (long)H * T; p.x2 = static_cast<const float *>(d_rs2); p.x2_bs = (long)H * T; p.x_split = H;
     }
-    return dispatch_convgemm<EPI_GATEBWD>(p, (hipStream_t)stream);
+    return conv_fwd_go(p, EPI_GATEBWD, true, (hipStream_t)stream);
 }
 
 extern "C" int glowtts_conv_gate_bwd(const float *d_rs, const float *d_rs2, const float *wp_b, const float *ts,
@@ -1101,9 +1171,11 @@ extern "C" int glowtts_conv_gate_bwd(const float *d_rs, const float *d_rs2, cons
     return glowtts_conv_gate_bwd_io(d_rs, d_rs2, wp_b, ts, drop, drop_scale, d_pre, nullptr, B, M_rs, H, T, 0, stream);
 }
 
-extern "C" int glowtts_conv_wrw2(const float *x, long x_bs, const float *d, long d_bs, const float *d2, long d2_bs,
-                                 int d_split, float *dwp, float *dbias, int B, int Cin, int M, int T, int taps, int dil,
-                                 int pad, glowtts_stream_t stream) {
+// The weight-gradient entries: `dry` = where glowtts_conv_wrw_batch, going problem by problem while a plan was asked for, collects it
+// (inner); the public entries take the calling thread's own.
+static int conv_wrw2(const float *x, long x_bs, const float *d, long d_bs, const float *d2, long d2_bs, int d_split, float *dwp,
+                     float *dbias, int B, int Cin, int M, int T, int taps, int dil, int pad, glowtts_stream_t stream, bool inner,
+                     ConvPlan *dry) {
     GLOWTTS_CHECK_ARG(x && d && d2 && dwp, "glowtts_conv_wrw2: null pointer");
     GLOWTTS_CHECK_ARG(B >= 0 && Cin > 0 && M > 0 && T >= 0 && d_split > 0 && d_split < M, "glowtts_conv_wrw2: bad shape");
     GLOWTTS_CHECK_ARG((taps == 1 || taps == 3 || taps == 5) && dil == 1 && pad == (taps - 1) / 2 && T % 4 == 0 &&
@@ -1115,61 +1187,37 @@ extern "C" int glowtts_conv_wrw2(const float *x, long x_bs, const float *d, long
     ConvWrwParams p{};
     p.x = x; p.d = d; p.d2 = d2; p.d2_bs = d2_bs; p.d_split = d_split; p.dwp = dwp; p.dbias = dbias; p.x_bs = x_bs; p.d_bs = d_bs;
     p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
-    hipStream_t s = (hipStream_t)stream;
-    if (int rc = conv_wrw_split_dispatch(p, s); rc >= 0) return rc;        // opt-in bf16-plane arithmetic
-    const bool n5 = (T % 80 == 0) || ((T + 79) / 80) * 80 <= ((T + 63) / 64) * 64;
-    if (taps == 5) return n5 ? launch_wrw_fp<5, 5>(p, s) : launch_wrw_fp<5, 4>(p, s);
-    if (taps == 3) return n5 ? launch_wrw_fp<3, 5>(p, s) : launch_wrw_fp<3, 4>(p, s);
-    return n5 ? launch_wrw_fp<1, 5>(p, s) : launch_wrw_fp<1, 4>(p, s);
+    return conv_wrw_go(p, 0, (hipStream_t)stream, inner ? dry : conv_plan_take());
 }
 
-extern "C" int glowtts_conv_wrw(const float *x, long x_bs, const float *d, long d_bs, const float *mask,
-                                const float *mask_x, float *dwp, float *dbias, int B, int Cin, int M, int T, int taps,
-                                int dil, int pad, glowtts_stream_t stream) {
+extern "C" int glowtts_conv_wrw2(const float *x, long x_bs, const float *d, long d_bs, const float *d2, long d2_bs,
+                                 int d_split, float *dwp, float *dbias, int B, int Cin, int M, int T, int taps, int dil,
+                                 int pad, glowtts_stream_t stream) {
+    return conv_wrw2(x, x_bs, d, d_bs, d2, d2_bs, d_split, dwp, dbias, B, Cin, M, T, taps, dil, pad, stream, false, nullptr);
+}
+
+static int conv_wrw(const float *x, long x_bs, const float *d, long d_bs, const float *mask, const float *mask_x, float *dwp,
+                    float *dbias, int B, int Cin, int M, int T, int taps, int dil, int pad, glowtts_stream_t stream, bool inner,
+                    ConvPlan *dry) {
     GLOWTTS_CHECK_ARG(x && d && dwp, "glowtts_conv_wrw: null pointer");
     GLOWTTS_CHECK_ARG(B >= 0 && Cin > 0 && M > 0 && T >= 0 && taps >= 1 && dil >= 1 && pad >= 0, "glowtts_conv_wrw: bad shape");
     if ((long)B * T == 0) return 0;
     ConvWrwParams p{};
     p.x = x; p.d = d; p.dwp = dwp; p.dbias = dbias; p.mask = mask; p.mask_x = mask_x; p.x_bs = x_bs; p.d_bs = d_bs;
     p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
-    const bool pipe_ok = (T % 4 == 0) && aligned16(x) && aligned16(d) && (x_bs % 4 == 0) && (d_bs % 4 == 0) &&
-                         (!mask || aligned16(mask)) && (!mask_x || aligned16(mask_x)) && ((taps - 1) * dil <= 12);
-    if (pipe_ok && (taps == 1 || taps == 3 || taps == 5)) {
-        hipStream_t s = (hipStream_t)stream;
-        if (dil == 1 && pad == (taps - 1) / 2) {         // frame-packed kernel: 80-frame chunks, or 64 when that wastes less
-            if (int rc = conv_wrw_split_dispatch(p, s); rc >= 0) return rc;        // opt-in bf16-plane arithmetic
-            const bool n5 = (T % 80 == 0) || ((T + 79) / 80) * 80 <= ((T + 63) / 64) * 64;
-            if (taps == 5) return n5 ? launch_wrw_fp<5, 5>(p, s) : launch_wrw_fp<5, 4>(p, s);
-            if (taps == 3) return n5 ? launch_wrw_fp<3, 5>(p, s) : launch_wrw_fp<3, 4>(p, s);
-            return n5 ? launch_wrw_fp<1, 5>(p, s) : launch_wrw_fp<1, 4>(p, s);
-        }
-        const bool c40 = (T % 40 == 0);
-        if (taps == 5) return c40 ? launch_wrw_pipe<5, 40>(p, s) : launch_wrw_pipe<5, 32>(p, s);
-        if (taps == 3) return c40 ? launch_wrw_pipe<3, 40>(p, s) : launch_wrw_pipe<3, 32>(p, s);
-        return c40 ? launch_wrw_pipe<1, 40>(p, s) : launch_wrw_pipe<1, 32>(p, s);
-    }
-    const int tiles = ((Cin + 63) / 64) * ((M + 127) / 128) * taps;
-    int splits = (768 + tiles - 1) / tiles;          // aim at ~3 workgroups per CU
-    if (splits > B) splits = B;
-    if (splits < 1) splits = 1;
-    p.nb = (B + splits - 1) / splits;
-    p.xs_pitch = pitch2(64);
-    p.ds_pitch = pitch2(64);
-    const size_t lds = ((size_t)64 * p.xs_pitch + (size_t)128 * p.ds_pitch) * sizeof(float);
-    dim3 grid(((Cin + 63) / 64) * ((M + 127) / 128), taps, (B + p.nb - 1) / p.nb);
-    hipLaunchKernelGGL(convwrw_kernel, grid, dim3(256), lds, (hipStream_t)stream, p);
-    if (dbias) {
-        hipError_t e0 = hipGetLastError();
-        if (e0 != hipSuccess) { set_error("glowtts_conv_wrw: launch failed: %s", hipGetErrorString(e0)); return (int)e0; }
-        return glowtts_rowsum(d, d_bs, mask, dbias, B, M, T, stream);
-    }
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw");
+    return conv_wrw_go(p, 0, (hipStream_t)stream, inner ? dry : conv_plan_take());
+}
+
+extern "C" int glowtts_conv_wrw(const float *x, long x_bs, const float *d, long d_bs, const float *mask,
+                                const float *mask_x, float *dwp, float *dbias, int B, int Cin, int M, int T, int taps,
+                                int dil, int pad, glowtts_stream_t stream) {
+    return conv_wrw(x, x_bs, d, d_bs, mask, mask_x, dwp, dbias, B, Cin, M, T, taps, dil, pad, stream, false, nullptr);
 }
 
 // Several weight gradients of ONE shape in one launch (dilation 1, 'same' padding): x[q] (B, Cin, T), d[q] (B, M, T) or, with d2,
 // rows [d_split, M) from d2[q]; dwp[q] / dbias[q] accumulated as in glowtts_conv_wrw; mask / mask_x (single-source form only) are
 // shared by the problems.  The arrays are HOST arrays of device pointers.  Without a kernel for the batch (native fp32 arithmetic,
-// other shapes) the problems are launched one by one.
+// other shapes: plan_conv_wrw says) the problems are launched one by one.
 extern "C" int glowtts_conv_wrw_batch(int n, const float *const *x, long x_bs, const float *const *d, long d_bs,
                                       const float *const *d2, long d2_bs, int d_split, const float *mask, const float *mask_x,
                                       float *const *dwp, float *const *dbias, int B, int Cin, int M, int T, int taps, int dil,
@@ -1179,34 +1227,30 @@ extern "C" int glowtts_conv_wrw_batch(int n, const float *const *x, long x_bs, c
     GLOWTTS_CHECK_ARG(B >= 0 && Cin > 0 && M > 0 && T >= 0 && taps >= 1 && dil >= 1 && pad >= 0, "glowtts_conv_wrw_batch: bad shape");
     GLOWTTS_CHECK_ARG(!d2 || (d_split > 0 && d_split < M), "glowtts_conv_wrw_batch: bad d_split");
     if ((long)B * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
+    ConvPlan *dry = conv_plan_take();
     for (int q0 = 0; q0 < n; q0 += ConvWrwParams::kMaxBatch) {
         const int nb = n - q0 < ConvWrwParams::kMaxBatch ? n - q0 : ConvWrwParams::kMaxBatch;
-        bool ok = nb > 1 && dil == 1 && pad == (taps - 1) / 2 && (taps == 1 || taps == 3 || taps == 5) && T % 4 == 0 &&
-                  x_bs % 4 == 0 && d_bs % 4 == 0 && (!d2 || (d2_bs % 4 == 0 && d_split % 64 == 0)) &&
-                  (!mask || aligned16(mask)) && (!mask_x || aligned16(mask_x));
-        ConvWrwParams p{};
-        for (int q = 0; q < nb && ok; ++q) {
-            const float *dq2 = d2 ? d2[q0 + q] : nullptr;
-            GLOWTTS_CHECK_ARG(x[q0 + q] && d[q0 + q] && dwp[q0 + q] && (!d2 || dq2), "glowtts_conv_wrw_batch: null pointer in problem %d", q0 + q);
-            ok = aligned16(x[q0 + q]) && aligned16(d[q0 + q]) && (!dq2 || aligned16(dq2));
-            p.bx[q] = x[q0 + q]; p.bd[q] = d[q0 + q]; p.bd2[q] = dq2; p.bdwp[q] = dwp[q0 + q];
-            p.bdbias[q] = dbias ? dbias[q0 + q] : nullptr;
-        }
-        if (ok) {
+        if (nb > 1) {
+            ConvWrwParams p{};
+            for (int q = 0; q < nb; ++q) {
+                const float *dq2 = d2 ? d2[q0 + q] : nullptr;
+                GLOWTTS_CHECK_ARG(x[q0 + q] && d[q0 + q] && dwp[q0 + q] && (!d2 || dq2), "glowtts_conv_wrw_batch: null pointer in problem %d", q0 + q);
+                p.bx[q] = x[q0 + q]; p.bd[q] = d[q0 + q]; p.bd2[q] = dq2; p.bdwp[q] = dwp[q0 + q];
+                p.bdbias[q] = dbias ? dbias[q0 + q] : nullptr;
+            }
             p.x = p.bx[0]; p.d = p.bd[0]; p.d2 = p.bd2[0]; p.dwp = p.bdwp[0]; p.dbias = p.bdbias[0];
             p.d2_bs = d2_bs; p.d_split = d_split; p.x_bs = x_bs; p.d_bs = d_bs; p.mask = mask; p.mask_x = mask_x;
             p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = dil; p.pad = pad;
             p.nbatch = nb;
-            const int rc = conv_wrw_split_dispatch(p, s);
+            const int rc = conv_wrw_go(p, 0, (hipStream_t)stream, dry);
             if (rc > 0) return rc;
             if (rc == 0) continue;
         }
         for (int q = q0; q < q0 + nb; ++q) {               // one by one
-            const int rc = d2 ? glowtts_conv_wrw2(x[q], x_bs, d[q], d_bs, d2[q], d2_bs, d_split, dwp[q], dbias ? dbias[q] : nullptr, B, Cin,
-                                                  M, T, taps, dil, pad, stream)
-                              : glowtts_conv_wrw(x[q], x_bs, d[q], d_bs, mask, mask_x, dwp[q], dbias ? dbias[q] : nullptr, B, Cin, M,
-                                                 T, taps, dil, pad, stream);
+            const int rc = d2 ? conv_wrw2(x[q], x_bs, d[q], d_bs, d2[q], d2_bs, d_split, dwp[q], dbias ? dbias[q] : nullptr, B, Cin, M, T,
+                                          taps, dil, pad, stream, true, dry)
+                              : conv_wrw(x[q], x_bs, d[q], d_bs, mask, mask_x, dwp[q], dbias ? dbias[q] : nullptr, B, Cin, M, T, taps,
+                                         dil, pad, stream, true, dry);
             if (rc != 0) return rc;
         }
     }
@@ -1245,13 +1289,5 @@ extern "C" int glowtts_rowsum(const float *d, long d_bs, const float *mask, floa
 }
 
 #ifdef GLOWTTS_TRACE
-extern "C" int glowtts_debug_trace_read(unsigned long long *host, int n_words, int clear) {
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(glowtts::g_trace), (size_t)n_words * 8);
-    if (e != hipSuccess) return (int)e;
-    if (clear) {
-        static unsigned long long zeros[8192 * 16];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(glowtts::g_trace), zeros, sizeof(zeros));
-    }
-    return (int)e;
-}
+extern "C" int glowtts_debug_trace_read(unsigned long long *host, int n_words, int clear) { return trace_read(host, n_words, clear); }
 #endif

@@ -14,6 +14,16 @@ __device__ __attribute__((aligned(16))) const float g_zero16[4] = {0.f, 0.f, 0.f
 static __device__ unsigned long long g_trace[8192 * 16];   // one copy per translation unit
 #define GLOWTTS_TRACE_POINT(i) do { if (threadIdx.x == 0) { g_trace[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 16 + (i)] = wall_clock64(); if ((i) == 3 || (i) == 4) g_trace[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 16 + 8 + (i)] = __builtin_readcyclecounter(); if ((i) == 0) { g_trace[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 16 + 15] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)); g_trace[((blockIdx.y * gridDim.x + blockIdx.x) & 8191) * 16 + 14] = 0x100 | __builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)); } } } while (0)
 #define GLOWTTS_TRACE_POINT_Z(i) do { if (threadIdx.x == 0) g_trace[((blockIdx.z * gridDim.x + blockIdx.x) & 8191) * 16 + (i)] = wall_clock64(); } while (0)
+// the body of a translation unit's glowtts_debug_trace_read*: its own g_trace to the host, optionally cleared
+static inline int trace_read(unsigned long long *host, int n_words, int clear) {
+    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_trace), (size_t)n_words * 8);
+    if (e != hipSuccess) return (int)e;
+    if (clear) {
+        static unsigned long long zeros[8192 * 16];
+        e = hipMemcpyToSymbol(HIP_SYMBOL(g_trace), zeros, sizeof(zeros));
+    }
+    return (int)e;
+}
 #else
 #define GLOWTTS_TRACE_POINT(i) do { } while (0)
 #define GLOWTTS_TRACE_POINT_Z(i) do { } while (0)
@@ -481,27 +491,5 @@ struct ConvWrwParams {
     float *bdwp[kMaxBatch], *bdbias[kMaxBatch];
     int nbatch;
 };
-
-// convgemm_split.hip: the frame-packed weight-gradient kernel on bf16 planes; -1 = not handled
-int conv_wrw_split_dispatch(ConvWrwParams &p, hipStream_t s);
-int conv_wrw_planes_dispatch(ConvWrwParams &p, int ns, hipStream_t s);
-// convwrw_tr.hip: the 5-tap weight gradient from frame-major LDS images (transposing LDS reads, two half-period groups per
-// workgroup); ns = planes per fp32 operand; -1 = not handled (other taps, M % 32, GLOWTTS_WRW_TR=0)
-int conv_wrw_tr_dispatch(ConvWrwParams &p, int ns, hipStream_t s);
-
-// convgemm_split.hip: bf16 TENSORS (p.xb): one bf16 plane of weights (bound with ns = 1), x loaded as bf16, the epilogue's
-// tensors bf16 or fp32 by p.yb; an error when the shape has no instantiation or no planes are bound (there is no
-// fp32 kernel that could read these tensors)
-int conv_bf16_dispatch(ConvGemmParams &p, int epi, bool big, bool n5, bool pipe_ok, hipStream_t s);
-
-// convwino.hip: the gated 5-tap in-conv in Winograd F(4, 5) form from U planes bound to the calling thread; -1 = not handled
-int conv_wino_gate_dispatch(ConvGemmParams &p, hipStream_t s);
-// convwino.hip: the backward-data of that conv (its packed backward weights) in the same form; -1 = not handled
-int conv_wino_bwd_dispatch(ConvGemmParams &p, hipStream_t s);
-int conv_math_forward();
-
-// convgemm_split.hip: bf16-plane arithmetic for the forward-type kernels; -1 = not handled (mode off / weights not
-// registered / shape not instantiated), otherwise the launch's return code
-int conv_split_dispatch(ConvGemmParams &p, int epi, bool big, int nct, bool pipe_ok, hipStream_t s);   // nct: 16-frame column tiles (5 / 4 / 2)
 
 }  // namespace glowtts

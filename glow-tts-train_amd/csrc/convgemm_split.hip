@@ -22,7 +22,7 @@
 //               a group pair in the A operand's order (pitch 80 B, the conflict-free pitch of the fp32 image), so one
 //               ds_read_b128 per plane is a B operand.
 #include <atomic>
-#include "convgemm_common.hpp"
+#include "conv_plan.hpp"
 #include "split_planes.hpp"
 
 namespace glowtts {
@@ -885,173 +885,105 @@ bool conv_find_planes(const float *wp, int ns, const unsigned short **out, long 
 int conv_math_forward() { return g_conv_math.load(std::memory_order_relaxed); }
 int conv_math_wrw() { return g_conv_math_wrw.load(std::memory_order_relaxed); }       // convwrw1.hip
 
-template <int NS, int RTW, int NCT, int EPI, int TAPS, int IOB = 0, int NSA = NS>
-static int launch_split(ConvGemmParams &p, const unsigned short *planes, long stride, hipStream_t s) {
-    constexpr int WGR = 64 * RTW, NT = 16 * NCT;
-    constexpr size_t lds_pipe = (size_t)NS * 3 * (NT + 16) * 80 + (size_t)(NT + 16) * sizeof(float);
-    constexpr size_t lds_epi = ((size_t)WGR * (NT + 4) + (EPI == EPI_GATEBWD ? 2 * WGR : 0)) * sizeof(float);
-    constexpr size_t lds = lds_pipe > lds_epi ? lds_pipe : lds_epi;
-    static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    p.vec_epilogue = aligned16(p.y0) && aligned16(p.y1) && aligned16(p.r0) && aligned16(p.r1) && aligned16(p.mask) &&
-                     aligned16(p.drop) && (p.y_bs % 4 == 0) && (p.r_bs % 4 == 0) && (EPI != EPI_GATE || p.H % 4 == 0);
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convgemm_split_kernel<NS, RTW, NCT, EPI, TAPS, IOB, NSA>), lds, "glowtts_conv (split)")) return rc_;
+// What a launch decision of the convolution family depends on besides its arguments (conv_plan.hpp): wp = the packed weights of a
+// forward-type launch (wino: also ask for their Winograd U planes), wrw = a weight gradient (the CU count where a plane mode is on).
+// Only the switches the planners read are filled in.
+ConvSnapshot conv_snapshot(const float *wp, bool wino, bool wrw) {
+    ConvSnapshot sn{};
+    sn.math_fwd = g_conv_math.load(std::memory_order_relaxed);
+    sn.math_wrw = g_conv_math_wrw.load(std::memory_order_relaxed);
+    if (!wrw) {
+        const PlaneBinding &b = t_bound;
+        if (b.wp != nullptr && wp >= b.wp && wp < b.wp + b.n) { sn.bound_ns = b.ns; sn.planes = b.planes + (wp - b.wp); sn.plane_stride = b.n; }
+        if (wino) conv_wino_bound(wp, &sn.wino_u, &sn.wino_stride);
+        for (Knob k : {K_CONV32_1X1, K_CONV_ROW_ADJ, K_WINO, K_WINO_BWD}) sn.knob[k] = knob(k);
+    } else if (sn.math_wrw != 0) {
+        sn.cus = compute_units();
+        for (Knob k : {K_WRW_TR, K_WRW_TR_MT, K_WRW_TR_NG, K_WRW_TR_NG_SPLITS, K_WRW_TR3, K_WRW_TR3_MT, K_WRW5_BSPLIT, K_WRW5_CUS}) sn.knob[k] = knob(k);
+    }
+    return sn;
+}
+
+// The forward-type instantiations as (epilogue, 64-row tiles per workgroup, taps), each with 80- and 64-frame tiles: ONE list for
+// "does the form exist" (the planner asks) and for the ladder.  The round-3 forms are the text encoder's 3-tap FFN convolutions
+// (attentions.py:347-381; forward, and backward-data as a forward-type convolution) when their ConvGroup's planes are bound —
+// fp32-equivalent arithmetic (NS = 3) only.
+// (round 4: the coupling's 1x1 start / end convolutions and their backward-data forms — 80 / 160 / 192 channels, 48 launches
+// per step on the decoder's chain — were instantiated here as EPI_PLAIN / EPI_ADD with one tap: under rocprofv3 the
+// bf16-plane forms take what the fp32-MFMA ones do (17.2 / 14.5 us against 16.4 / 15.3 in the step, 8.7 against 8.0 us at
+// best) and the step does not move (14.89 against 14.92 ms): these launches are their fixed costs.  Not kept.)
+#define GLOWTTS_SPLIT_FORMS(X) \
+    X(EPI_GATE, 2, 5) X(EPI_RESSKIP, 2, 1) X(EPI_RESSKIP_LAST, 1, 1) X(EPI_GATEBWD, 1, 1) X(EPI_ADD, 1, 5) X(EPI_PLAIN, 1, 5)
+#define GLOWTTS_SPLIT_FORMS_NS3(X) X(EPI_PLAIN, 1, 3) X(EPI_PLAIN, 2, 3) X(EPI_ADD, 1, 3) X(EPI_ADD, 2, 3)
+// bf16 tensors (the instantiations a flow block needs: csrc/wn_stack.hip, io = 1): the forms above, and the 1x1 convolutions with
+// fp32 OR bf16 results (start, end, start's input gradient added into an fp32 flow gradient)
+#define GLOWTTS_BF16_FORMS_1X1(X) X(EPI_PLAIN, 1, 1) X(EPI_ADD, 1, 1)
+#define GLOWTTS_FORM_EXISTS(E, R, TP) if (epi == E && rows == 64 * R && taps == TP) return true;
+
+bool conv_split_has(int ns, int epi, int rows, int taps, int nt) {
+    // 32-frame tiles: only the 64-row form pays (rocprofv3, T = 160: 192 <- 768 channels 50.0 -> 45.4 us; the 128-row form
+    // of 768 <- 192 channels measured 47.3 us against 45.3 native: it stays on the fp32 MFMA kernel)
+    if (nt == 32) return ns == 3 && epi == EPI_PLAIN && taps == 3 && rows == 64;
+    GLOWTTS_SPLIT_FORMS(GLOWTTS_FORM_EXISTS)
+    if (ns == 3) { GLOWTTS_SPLIT_FORMS_NS3(GLOWTTS_FORM_EXISTS) }
+    return false;
+}
+bool conv_bf16_has(int iob, int epi, int rows, int taps) {
+    GLOWTTS_BF16_FORMS_1X1(GLOWTTS_FORM_EXISTS)
+    if (iob == 1) { GLOWTTS_SPLIT_FORMS(GLOWTTS_FORM_EXISTS) }
+    return false;
+}
+
+template <int NS, int IOB, int NSA>
+static int launch_split_ns(const ConvGemmParams &p, const ConvPlan &plan, const ConvSnapshot &sn, hipStream_t s) {
+#define GLOWTTS_FORM_LAUNCH(E, R, TP)                                                                                                   \
+    if (plan.epi == E && plan.rows == 64 * R && plan.taps == TP) {                                                                      \
+        static_assert(lds_conv_split(NS, 64 * R, 80, E) <= 80 * 1024, "two workgroups per CU");                                         \
+        return plan.frame_tile == 80 ? launch_planned<&convgemm_split_kernel<NS, R, 5, E, TP, IOB, NSA>>(plan, "glowtts_conv (split)", s, p, sn.planes, sn.plane_stride) \
+                                     : launch_planned<&convgemm_split_kernel<NS, R, 4, E, TP, IOB, NSA>>(plan, "glowtts_conv (split)", s, p, sn.planes, sn.plane_stride); \
+    }
+    if constexpr (IOB != 0) {
+        GLOWTTS_BF16_FORMS_1X1(GLOWTTS_FORM_LAUNCH)
+        if constexpr (IOB == 1) { GLOWTTS_SPLIT_FORMS(GLOWTTS_FORM_LAUNCH) }
+    } else {
+        if constexpr (NS == 3)
+            if (plan.frame_tile == 32) return launch_planned<&convgemm_split_kernel<3, 1, 2, EPI_PLAIN, 3>>(plan, "glowtts_conv (split)", s, p, sn.planes, sn.plane_stride);
+        GLOWTTS_SPLIT_FORMS(GLOWTTS_FORM_LAUNCH)
+        if constexpr (NS == 3) { GLOWTTS_SPLIT_FORMS_NS3(GLOWTTS_FORM_LAUNCH) }
+    }
+#undef GLOWTTS_FORM_LAUNCH
+    set_error("glowtts_conv (split): planned a form that does not exist (epilogue %d, rows %d, taps %d)", plan.epi, plan.rows, plan.taps);
+    return 1;
+}
+
+int launch_conv_split(ConvGemmParams &p, const ConvPlan &plan, const ConvSnapshot &sn, hipStream_t s) {
+    p.vec_epilogue = plan.vec_epilogue;
+    p.wg_order = plan.wg_order;
     p.exp = GLOWTTS_EXP_BITS(knob(K_CONV_EXP));
-    const int ntile_t = (p.T + NT - 1) / NT;
-    const int rows = (EPI == EPI_GATE) ? p.H : p.M;
-    const int per = (EPI == EPI_GATE) ? 64 : WGR;
-    dim3 grid(ntile_t * p.B, (rows + per - 1) / per);
-    p.wg_order = (grid.y > 1 && grid.x % 8 == 0 && knob(K_CONV_ROW_ADJ) == 1) ? 1 : 0;
-    hipLaunchKernelGGL((convgemm_split_kernel<NS, RTW, NCT, EPI, TAPS, IOB, NSA>), grid, dim3(256), lds, s, p, planes, stride);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv (split)");
+    if (plan.iob == 1) return launch_split_ns<1, 1, 1>(p, plan, sn, s);
+    if (plan.iob == 2) return launch_split_ns<1, 2, 3>(p, plan, sn, s);
+    if (plan.ns == 3) return launch_split_ns<3, 0, 3>(p, plan, sn, s);
+    if (plan.ns == 2) return launch_split_ns<2, 0, 2>(p, plan, sn, s);
+    return launch_split_ns<1, 0, 1>(p, plan, sn, s);
 }
 
-// bf16 tensors: the instantiations a flow block needs (csrc/wn_stack.hip, io = 1)
-template <int IOB>
-static int dispatch_bf16_io(ConvGemmParams &p, int epi, bool big, bool n5, const unsigned short *pl, long st, hipStream_t s) {
-#define GLOWTTS_BF16_CASE(E, R, TP)                                                    \
-    if (epi == E && (R == 2) == big && p.taps == TP)                                   \
-        return n5 ? launch_split<1, R, 5, E, TP, IOB, (IOB == 2 ? 3 : 1)>(p, pl, st, s)  \
-                  : launch_split<1, R, 4, E, TP, IOB, (IOB == 2 ? 3 : 1)>(p, pl, st, s);
-    // the 1x1 PLAIN / ADD convolutions (start, end, start's input gradient) exist with 64-row workgroups only, which serve
-    // any M: dispatch_convgemm's 128-row preference (M % 128 == 0 or M > 192: squeezed C = 128 / 256) must not leave them
-    // without a kernel
-    if (p.taps == 1 && (epi == EPI_PLAIN || epi == EPI_ADD)) big = false;
-    GLOWTTS_BF16_CASE(EPI_PLAIN, 1, 1)       // fp32 results (IOB == 2): exact weights, three planes
-    GLOWTTS_BF16_CASE(EPI_ADD, 1, 1)         // ... and the start conv's input gradient added into an fp32 flow gradient
-    if constexpr (IOB == 1) {
-        GLOWTTS_BF16_CASE(EPI_GATE, 2, 5)
-        GLOWTTS_BF16_CASE(EPI_RESSKIP, 2, 1)
-        GLOWTTS_BF16_CASE(EPI_RESSKIP_LAST, 1, 1)
-        GLOWTTS_BF16_CASE(EPI_GATEBWD, 1, 1)
-        GLOWTTS_BF16_CASE(EPI_ADD, 1, 5)
-        GLOWTTS_BF16_CASE(EPI_PLAIN, 1, 5)
-    }
-#undef GLOWTTS_BF16_CASE
-    return -1;
+// the ladder of the frame-packed bf16-plane weight gradients: operands split while they are staged, or given as planes (PRE)
+template <int NS, bool PRE>
+static int launch_wrw_split_ns(const ConvWrwParams &p, const ConvPlan &plan, hipStream_t s) {
+    static_assert(lds_wrw_split(NS, 80, 64) <= 80 * 1024, "two workgroups per CU");
+    const char *who = PRE ? "glowtts_conv_wrw_planes" : "glowtts_conv_wrw (split)";
+    const bool n5 = plan.frame_tile == 80;
+    if (plan.taps == 5)
+        return n5 ? launch_planned<&convwrw_split_kernel<NS, 5, 5, 2, PRE>>(plan, who, s, p) : launch_planned<&convwrw_split_kernel<NS, 5, 4, 2, PRE>>(plan, who, s, p);
+    return n5 ? launch_planned<&convwrw_split_kernel<NS, 1, 5, 4, PRE>>(plan, who, s, p) : launch_planned<&convwrw_split_kernel<NS, 1, 4, 4, PRE>>(plan, who, s, p);
 }
 
-template <int NS>
-static int dispatch_split_ns(ConvGemmParams &p, int epi, bool big, int nct, const unsigned short *pl, long st, hipStream_t s) {
-    const bool n5 = nct == 5;
-#define GLOWTTS_SPLIT_CASE(E, R, TP)                                                   \
-    if (epi == E && (R == 2) == big && p.taps == TP && nct != 2)                       \
-        return n5 ? launch_split<NS, R, 5, E, TP>(p, pl, st, s) : launch_split<NS, R, 4, E, TP>(p, pl, st, s);
-    GLOWTTS_SPLIT_CASE(EPI_GATE, 2, 5)
-    GLOWTTS_SPLIT_CASE(EPI_RESSKIP, 2, 1)
-    GLOWTTS_SPLIT_CASE(EPI_RESSKIP_LAST, 1, 1)
-    GLOWTTS_SPLIT_CASE(EPI_GATEBWD, 1, 1)
-    GLOWTTS_SPLIT_CASE(EPI_ADD, 1, 5)
-    GLOWTTS_SPLIT_CASE(EPI_PLAIN, 1, 5)
-    // round 3: the text encoder's 3-tap FFN convolutions (attentions.py:347-381; forward, and backward-data as a forward-type
-    // convolution) when their ConvGroup's planes are bound — fp32-equivalent form only; with 32-frame tiles where the native
-    // dispatch would pick them (T_text = 160: 80-frame tiles leave a quarter of the CUs without a workgroup)
-    if constexpr (NS == 3) {
-        // (round 4: the coupling's 1x1 start / end convolutions and their backward-data forms — 80 / 160 / 192 channels, 48 launches
-        // per step on the decoder's chain — were instantiated here as EPI_PLAIN / EPI_ADD with one tap: under rocprofv3 the
-        // bf16-plane forms take what the fp32-MFMA ones do (17.2 / 14.5 us against 16.4 / 15.3 in the step, 8.7 against 8.0 us at
-        // best) and the step does not move (14.89 against 14.92 ms): these launches are their fixed costs.  Not kept.)
-        GLOWTTS_SPLIT_CASE(EPI_PLAIN, 1, 3)
-        GLOWTTS_SPLIT_CASE(EPI_PLAIN, 2, 3)
-        GLOWTTS_SPLIT_CASE(EPI_ADD, 1, 3)
-        GLOWTTS_SPLIT_CASE(EPI_ADD, 2, 3)
-        // 32-frame tiles: only the 64-row form pays (rocprofv3, T = 160: 192 <- 768 channels 50.0 -> 45.4 us; the 128-row form
-        // of 768 <- 192 channels measured 47.3 us against 45.3 native: it stays on the fp32 MFMA kernel)
-        if (epi == EPI_PLAIN && p.taps == 3 && nct == 2 && !big) return launch_split<NS, 1, 2, EPI_PLAIN, 3>(p, pl, st, s);
-    }
-#undef GLOWTTS_SPLIT_CASE
-    return -1;
-}
-
-template <int NS, int TAPS, int NGRP, int MT>
-static int launch_wrw_split(ConvWrwParams &p, hipStream_t s) {
-    constexpr int CT = 16 * NGRP, MR = 16 * MT;
-    constexpr size_t lds = (size_t)NS * (64 + MR) * 104 * 2 + (size_t)(CT + 8 + CT + 64) * sizeof(float);
-    static_assert(lds <= 80 * 1024, "two workgroups per CU");
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convwrw_split_kernel<NS, TAPS, NGRP, MT>), lds, "glowtts_conv_wrw (split)")) return rc_;
-    const int tiles = ((p.Cin + 63) / 64) * ((p.M + MR - 1) / MR);
-    const int total = p.B * ((p.T + CT - 1) / CT);
-    int splits = 512 / tiles;                       // all workgroups resident at once (2 per CU; 256 / 128 slots for the single
-                                                    // launches measured 15.08 / 15.17 ms per step against 15.11: no gain)
-    if (splits > total) splits = total;
-    if (splits < 1) splits = 1;
-    p.nb = (total + splits - 1) / splits;
+int launch_wrw_split(ConvWrwParams &p, const ConvPlan &plan, hipStream_t s) {
+    if (plan.family == GLOWTTS_PLAN_WRW_PLANES) return plan.ns == 3 ? launch_wrw_split_ns<3, true>(p, plan, s) : launch_wrw_split_ns<1, true>(p, plan, s);
     p.ds_pitch = knob(K_WRW1_PIPE) == 0 ? 1 : 0;                   // 1x1 kernel: 1 = the unpipelined loop (tuning / A-B switch)
-    dim3 grid(tiles, 1, ((total + p.nb - 1) / p.nb) * (p.nbatch > 0 ? p.nbatch : 1));
-    hipLaunchKernelGGL((convwrw_split_kernel<NS, TAPS, NGRP, MT>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw (split)");
-}
-
-template <int NS, int TAPS, int NGRP, int MT>
-static int launch_wrw_planes(ConvWrwParams &p, hipStream_t s) {
-    constexpr int CT = 16 * NGRP, MR = 16 * MT;
-    constexpr size_t lds = (size_t)NS * (64 + MR) * 104 * 2 + (size_t)(CT + 8 + CT + 64) * sizeof(float);
-    static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convwrw_split_kernel<NS, TAPS, NGRP, MT, true>), lds, "glowtts_conv_wrw_planes")) return rc_;
-    const int tiles = ((p.Cin + 63) / 64) * ((p.M + MR - 1) / MR);
-    const int total = p.B * ((p.T + CT - 1) / CT);
-    int splits = 512 / tiles;
-    if (splits > total) splits = total;
-    if (splits < 1) splits = 1;
-    p.nb = (total + splits - 1) / splits;
-    dim3 grid(tiles, 1, (total + p.nb - 1) / p.nb);
-    hipLaunchKernelGGL((convwrw_split_kernel<NS, TAPS, NGRP, MT, true>), grid, dim3(256), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw_planes");
-}
-
-int conv_wrw_planes_dispatch(ConvWrwParams &p, int ns, hipStream_t s) {
-    const bool n5 = (p.T % 80 == 0) || ((p.T + 79) / 80) * 80 <= ((p.T + 63) / 64) * 64;
-    if (ns == 3 && p.taps == 5 && p.M % 32 == 0) return n5 ? launch_wrw_planes<3, 5, 5, 2>(p, s) : launch_wrw_planes<3, 5, 4, 2>(p, s);
-    if (ns == 3 && p.taps == 1) return n5 ? launch_wrw_planes<3, 1, 5, 4>(p, s) : launch_wrw_planes<3, 1, 4, 4>(p, s);
-    // one plane = the tensors ARE bf16 (flow blocks with bf16 activations in HBM)
-    if (ns == 1 && p.taps == 5 && p.M % 32 == 0) return n5 ? launch_wrw_planes<1, 5, 5, 2>(p, s) : launch_wrw_planes<1, 5, 4, 2>(p, s);
-    if (ns == 1 && p.taps == 1) return n5 ? launch_wrw_planes<1, 1, 5, 4>(p, s) : launch_wrw_planes<1, 1, 4, 4>(p, s);
-    return -1;
-}
-
-template <int NS>
-static int dispatch_wrw_split_ns(ConvWrwParams &p, hipStream_t s) {
-    const bool n5 = (p.T % 80 == 0) || ((p.T + 79) / 80) * 80 <= ((p.T + 63) / 64) * 64;
-    if (p.taps == 5 && p.M % 32 == 0 && (!p.d2 || p.d_split % 32 == 0))
-        return n5 ? launch_wrw_split<NS, 5, 5, 2>(p, s) : launch_wrw_split<NS, 5, 4, 2>(p, s);
-    if (p.taps == 1) return n5 ? launch_wrw_split<NS, 1, 5, 4>(p, s) : launch_wrw_split<NS, 1, 4, 4>(p, s);
-    return -1;
-}
-
-// called by the frame-packed weight-gradient entries (dilation 1, 'same' padding, 16-byte rows already checked)
-int conv_wrw_split_dispatch(ConvWrwParams &p, hipStream_t s) {
-    const int ns = g_conv_math_wrw.load(std::memory_order_relaxed);
-    if (ns != 0)                                   // 5-tap convolutions: the frame-major / transposed-read kernel (convwrw_tr.hip)
-        if (int rc = conv_wrw_tr_dispatch(p, ns, s); rc >= 0) return rc;
-    if (ns == 3) return dispatch_wrw_split_ns<3>(p, s);
-    if (ns == 2) return dispatch_wrw_split_ns<2>(p, s);
-    if (ns == 1) return dispatch_wrw_split_ns<1>(p, s);
-    return -1;
-}
-
-int conv_bf16_dispatch(ConvGemmParams &p, int epi, bool big, bool n5, bool pipe_ok, hipStream_t s) {
-    GLOWTTS_CHECK_ARG(pipe_ok && (p.T % 4) == 0, "glowtts_conv (bf16 tensors): needs T %% 4 == 0 and 16-byte aligned rows");
-    const unsigned short *pl = nullptr;
-    long st = 0;
-    GLOWTTS_CHECK_ARG(find_planes(p.wp, 3, &pl, &st), "glowtts_conv (bf16 tensors): the packed weights have no bf16 planes bound "
-                      "(glowtts_split_planes(wp, n, planes, 3) + glowtts_conv_bind_planes_ns(wp, n, planes, 3))");
-    const int rc = p.yb ? dispatch_bf16_io<1>(p, epi, big, n5, pl, st, s) : dispatch_bf16_io<2>(p, epi, big, n5, pl, st, s);
-    GLOWTTS_CHECK_ARG(rc >= 0, "glowtts_conv (bf16 tensors): no kernel for epilogue %d, taps %d, M %d, output %s", epi, p.taps, p.M,
-                      p.yb ? "bf16" : "fp32");
-    return rc;
-}
-
-// called first by dispatch_convgemm: -1 = not handled here (mode off, weights not registered, shape not instantiated)
-int conv_split_dispatch(ConvGemmParams &p, int epi, bool big, int nct, bool pipe_ok, hipStream_t s) {
-    const int ns = g_conv_math.load(std::memory_order_relaxed);
-    if (ns == 0 || !pipe_ok) return -1;
-    const unsigned short *pl = nullptr;
-    long st = 0;
-    if (!find_planes(p.wp, ns, &pl, &st)) return -1;
-    if (ns == 3) return dispatch_split_ns<3>(p, epi, big, nct, pl, st, s);
-    if (ns == 2) return dispatch_split_ns<2>(p, epi, big, nct, pl, st, s);
-    return dispatch_split_ns<1>(p, epi, big, nct, pl, st, s);
+    if (plan.ns == 3) return launch_wrw_split_ns<3, false>(p, plan, s);
+    if (plan.ns == 2) return launch_wrw_split_ns<2, false>(p, plan, s);
+    return launch_wrw_split_ns<1, false>(p, plan, s);
 }
 
 }  // namespace glowtts
@@ -1117,20 +1049,9 @@ extern "C" int glowtts_conv_wrw_planes(const unsigned short *x_planes, long x_pl
     p.xpl = x_planes; p.dpl = d_planes; p.xpl_stride = x_plane_stride; p.dpl_stride = d_plane_stride;
     p.dwp = dwp; p.dbias = dbias; p.x_bs = x_bs; p.d_bs = d_bs;
     p.B = B; p.Cin = Cin; p.M = M; p.T = T; p.taps = taps; p.dil = 1; p.pad = (taps - 1) / 2;
-    const int rc = conv_wrw_planes_dispatch(p, n_planes, (hipStream_t)stream);
-    GLOWTTS_CHECK_ARG(rc >= 0, "glowtts_conv_wrw_planes: no kernel for taps=%d, M=%d, planes=%d (3 planes; 5 taps with M %% 32 == 0, or 1 tap)",
-                      taps, M, n_planes);
-    return rc;
+    return conv_wrw_go(p, n_planes, (hipStream_t)stream, conv_plan_take());
 }
 
 #ifdef GLOWTTS_TRACE
-extern "C" int glowtts_debug_trace_read_split(unsigned long long *host, int n_words, int clear) {
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(glowtts::g_trace), (size_t)n_words * 8);
-    if (e != hipSuccess) return (int)e;
-    if (clear) {
-        static unsigned long long zeros[8192 * 16];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(glowtts::g_trace), zeros, sizeof(zeros));
-    }
-    return (int)e;
-}
+extern "C" int glowtts_debug_trace_read_split(unsigned long long *host, int n_words, int clear) { return glowtts::trace_read(host, n_words, clear); }
 #endif

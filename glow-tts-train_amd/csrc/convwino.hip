@@ -17,7 +17,7 @@
 // 3 x (2 channels x 4 frames; the halo frames come from the neighbouring lanes by DPP), transforms, splits and stores into the
 // OTHER of two LDS images while the MFMAs read this one.  One wave per SIMD also means that nothing hides a stall: the staging and
 // the epilogue are written as PINNED instructions in stages of independent operations (lesson 43).
-#include "convgemm_common.hpp"
+#include "conv_plan.hpp"
 #include "split_planes.hpp"
 #include <algorithm>
 #include <atomic>
@@ -667,42 +667,45 @@ struct WinoBinding {
 static thread_local WinoBinding t_wino;
 static std::atomic<long> g_wino_launches{0};      // launches of the Winograd kernel so far (tests / bench.py ask: did it run?)
 
-// -1 = not handled (switch off, no U planes bound for these weights, shape or alignment outside the kernel's)
-int conv_wino_gate_dispatch(ConvGemmParams &p, hipStream_t s) {
-    if (!knob(K_WINO) || conv_math_forward() != 3) return -1;
+// the U planes bound to the calling thread for the packed weights at wp (conv_snapshot), or null
+void conv_wino_bound(const float *wp, const unsigned short **U, long *stride) {
     const WinoBinding &w = t_wino;
-    if (w.wp == nullptr || p.wp < w.wp || p.wp >= w.wp + w.n) return -1;
-    if (p.taps != 5 || p.dil != 1 || p.pad != 2 || p.xb || p.yb || p.x2 || p.mask_in) return -1;
-    if (p.H % 64 != 0 || p.Cin % 32 != 0 || p.M != 2 * p.H || p.T % 4 != 0) return -1;
-    if (!aligned16(p.x) || !aligned16(p.y0) || !aligned16(p.y1) || !aligned16(p.drop) || (long)p.B * p.x_bs * 4 >= 0x7ffffff0L) return -1;
-    const unsigned short *U = w.planes + wino_u_offset(p.wp - w.wp);
-    const size_t lds = (size_t)2 * WinoTile<FWD_GATE>::IMG_DW * sizeof(float);
-    static LdsLimit attr_max_e;
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&wino_gate_fwd_kernel<0>), lds, "glowtts_conv_gate_fwd (Winograd)")) return rc_;
-    const int n_tiles = p.B * (p.T / 4);
+    if (w.wp == nullptr || wp < w.wp || wp >= w.wp + w.n) return;
+    *U = w.planes + wino_u_offset(wp - w.wp);
+    *stride = w.stride;
+}
+
+// false = not this kernel's (switch off, no U planes bound for these weights, shape or alignment outside the kernel's)
+bool plan_wino_gate(const ConvGemmParams &p, const ConvSnapshot &sn, ConvPlan &plan) {
+    if (!sn.knob[K_WINO] || sn.math_fwd != 3 || sn.wino_u == nullptr) return false;
+    if (p.taps != 5 || p.dil != 1 || p.pad != 2 || p.xb || p.yb || p.x2 || p.mask_in) return false;
+    if (p.H % 64 != 0 || p.Cin % 32 != 0 || p.M != 2 * p.H || p.T % 4 != 0) return false;
+    if (!aligned16(p.x) || !aligned16(p.y0) || !aligned16(p.y1) || !aligned16(p.drop) || (long)p.B * p.x_bs * 4 >= 0x7ffffff0L) return false;
     constexpr int WINO_COLS = WinoTile<FWD_GATE>::COLS;
-    dim3 grid((unsigned)(((n_tiles + WINO_COLS - 1) / WINO_COLS) * (p.H / 64)));
+    plan.family = GLOWTTS_PLAN_WINO_GATE;
+    plan.ns = plan.nsa = 3; plan.rows = 64; plan.frame_tile = 4 * WINO_COLS; plan.taps = 5;
+    plan.lds_bytes = (int)((size_t)2 * WinoTile<FWD_GATE>::IMG_DW * sizeof(float));
+    plan.grid_x = ((p.B * (p.T / 4) + WINO_COLS - 1) / WINO_COLS) * (p.H / 64);
+    plan.grid_y = plan.grid_z = 1;
+    return true;
+}
+
+int launch_wino_gate(ConvGemmParams &p, const ConvPlan &plan, const ConvSnapshot &sn, hipStream_t s) {
+    const char *who = "glowtts_conv_gate_fwd (Winograd)";
 #ifdef GLOWTTS_TRACE
     // timing experiments of the tuning build (tools/wino_bench.py; results WRONG): GLOWTTS_WINO = 1 + 2 x {1: no split / store of the
     // next image, 3: no staging at all, 7: six independent FMAs behind every MFMA pair instead of the staging, 8: the input loads
     // are waited for and nothing is computed}
-    const int exp = knob(K_WINO) >> 1;
-    if (exp == 1 || exp == 3 || exp == 7 || exp == 8) {
-        static LdsLimit attr_x[4];
-        const int slot = exp == 1 ? 0 : exp == 3 ? 1 : exp == 7 ? 2 : 3;
-        const void *fn = exp == 1 ? reinterpret_cast<const void *>(&wino_gate_fwd_kernel<1>) : exp == 3 ? reinterpret_cast<const void *>(&wino_gate_fwd_kernel<3>)
-                       : exp == 7 ? reinterpret_cast<const void *>(&wino_gate_fwd_kernel<7>) : reinterpret_cast<const void *>(&wino_gate_fwd_kernel<8>);
-        if (int rc_ = attr_x[slot].ensure(fn, lds, "glowtts_conv_gate_fwd (Winograd)")) return rc_;
-        if (exp == 1) hipLaunchKernelGGL(wino_gate_fwd_kernel<1>, grid, dim3(256), lds, s, p, U, w.stride);
-        else if (exp == 3) hipLaunchKernelGGL(wino_gate_fwd_kernel<3>, grid, dim3(256), lds, s, p, U, w.stride);
-        else if (exp == 7) hipLaunchKernelGGL(wino_gate_fwd_kernel<7>, grid, dim3(256), lds, s, p, U, w.stride);
-        else hipLaunchKernelGGL(wino_gate_fwd_kernel<8>, grid, dim3(256), lds, s, p, U, w.stride);
-        GLOWTTS_LAUNCH_CHECK("glowtts_conv_gate_fwd (Winograd)");
+    switch (sn.knob[K_WINO] >> 1) {
+    case 1: return launch_planned<&wino_gate_fwd_kernel<1>>(plan, who, s, p, sn.wino_u, sn.wino_stride);
+    case 3: return launch_planned<&wino_gate_fwd_kernel<3>>(plan, who, s, p, sn.wino_u, sn.wino_stride);
+    case 7: return launch_planned<&wino_gate_fwd_kernel<7>>(plan, who, s, p, sn.wino_u, sn.wino_stride);
+    case 8: return launch_planned<&wino_gate_fwd_kernel<8>>(plan, who, s, p, sn.wino_u, sn.wino_stride);
+    default: break;
     }
 #endif
     g_wino_launches.fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(wino_gate_fwd_kernel<0>, grid, dim3(256), lds, s, p, U, w.stride);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_gate_fwd (Winograd)");
+    return launch_planned<&wino_gate_fwd_kernel<0>>(plan, who, s, p, sn.wino_u, sn.wino_stride);
 }
 
 // Workspace of the backward kernel: per (device, stream) — two eager launches on different streams never share partials or
@@ -753,32 +756,33 @@ static int wino_bwd_workspace(hipStream_t s, long n_groups, float **partials, un
     return 0;
 }
 
-// -1 = not handled: the backward-data of the gated in-conv (the in-conv's packed backward weights, M rows, Cin = 2 M input
+// false = not this kernel's: the backward-data of the gated in-conv (the in-conv's packed backward weights, M rows, Cin = 2 M input
 // channels, 5 taps, pad 2) in Winograd form where its U planes are bound, the switch GLOWTTS_WINO_BWD is on and the shape fits
-int conv_wino_bwd_dispatch(ConvGemmParams &p, hipStream_t s) {
-    if (!knob(K_WINO_BWD) || conv_math_forward() != 3) return -1;
-    const WinoBinding &w = t_wino;
-    if (w.wp == nullptr || p.wp < w.wp || p.wp >= w.wp + w.n) return -1;
+bool plan_wino_bwd(const ConvGemmParams &p, const ConvSnapshot &sn, ConvPlan &plan) {
+    if (!sn.knob[K_WINO_BWD] || sn.math_fwd != 3 || sn.wino_u == nullptr) return false;
     if (p.taps != 5 || p.dil != 1 || p.pad != 2 || p.xb || p.yb || p.x2 || p.mask_in || p.mask_add || p.bias || p.relu || p.drop ||
         p.gate_pos)
-        return -1;
-    if (p.M != 192 || p.Cin != 2 * p.M || p.T % 4 != 0) return -1;
+        return false;
+    if (p.M != 192 || p.Cin != 2 * p.M || p.T % 4 != 0) return false;
     if (!aligned16(p.x) || !aligned16(p.y0) || !aligned16(p.r0) || (p.mask_out && !aligned16(p.mask)) || p.x_bs % 4 || p.y_bs % 4 ||
         (p.r0 && p.r_bs % 4) || (long)p.B * p.x_bs * 4 >= 0x7ffffff0L)
-        return -1;
-    const int n_tiles = p.B * (p.T / 4);
+        return false;
     constexpr int COLS = WinoTile<BWD_HALF>::COLS;
-    const long n_groups = (n_tiles + COLS - 1) / COLS;
+    plan.family = GLOWTTS_PLAN_WINO_BWD;
+    plan.ns = plan.nsa = 3; plan.rows = p.M; plan.frame_tile = 4 * COLS; plan.taps = 5;
+    plan.lds_bytes = (int)((size_t)2 * WinoTile<BWD_HALF>::IMG_DW * sizeof(float));
+    plan.grid_x = 2 * ((p.B * (p.T / 4) + COLS - 1) / COLS);      // two workgroups (halves of the input channels) per column group
+    plan.grid_y = plan.grid_z = 1;
+    return true;
+}
+
+// -1 = the workspace cannot be had now (see above): the caller launches the direct plan instead
+int launch_wino_bwd(ConvGemmParams &p, const ConvPlan &plan, const ConvSnapshot &sn, hipStream_t s) {
     float *ws = nullptr;
     unsigned *cnt = nullptr;
-    if (wino_bwd_workspace(s, n_groups, &ws, cnt) != 0) return -1;
-    const unsigned short *U = w.planes + wino_u_offset(p.wp - w.wp);
-    const size_t lds = (size_t)2 * WinoTile<BWD_HALF>::IMG_DW * sizeof(float);
-    static LdsLimit attr_max_b;
-    if (int rc_ = attr_max_b.ensure(reinterpret_cast<const void *>(&wino_bwd_kernel), lds, "glowtts_conv_fwd (Winograd backward-data)")) return rc_;
+    if (wino_bwd_workspace(s, plan.grid_x / 2, &ws, cnt) != 0) return -1;
     g_wino_bwd_launches.fetch_add(1, std::memory_order_relaxed);
-    hipLaunchKernelGGL(wino_bwd_kernel, dim3((unsigned)(2 * n_groups)), dim3(256), lds, s, p, U, w.stride, ws, cnt);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_fwd (Winograd backward-data)");
+    return launch_planned<&wino_bwd_kernel>(plan, "glowtts_conv_fwd (Winograd backward-data)", s, p, sn.wino_u, sn.wino_stride, ws, cnt);
 }
 
 }  // namespace glowtts
@@ -810,13 +814,5 @@ extern "C" int glowtts_conv_bind_wino(const float *wp, long n, const unsigned sh
 }
 
 #ifdef GLOWTTS_TRACE
-extern "C" int glowtts_debug_trace_read_wino(unsigned long long *host, int n_words, int clear) {
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(glowtts::g_trace), (size_t)n_words * 8);
-    if (e != hipSuccess) return (int)e;
-    if (clear) {
-        static unsigned long long zeros[8192 * 16];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(glowtts::g_trace), zeros, sizeof(zeros));
-    }
-    return (int)e;
-}
+extern "C" int glowtts_debug_trace_read_wino(unsigned long long *host, int n_words, int clear) { return glowtts::trace_read(host, n_words, clear); }
 #endif

@@ -23,7 +23,7 @@
 // A 32-lane half therefore reads 8 frames of equal parity, which with the pitches below (36 / 20 dwords: 4 mod 8) fall on
 // 8 disjoint groups of 8 banks; the staging stores (one dword = a channel PAIR of one frame, as v_cvt_pk_bf16_f32 leaves it)
 // go 16 pairs x 2 frame quads per half-wave, again conflict-free with these pitches.
-#include "convgemm_common.hpp"
+#include "conv_plan.hpp"
 #include "split_planes.hpp"
 
 #include <cstdlib>
@@ -484,7 +484,7 @@ __global__ __launch_bounds__(256 * NG, 2) void convwrw_tr_kernel(ConvWrwParams p
 #endif
 }
 
-static int compute_units() {
+int compute_units() {
     static int n[kMaxDevices] = {0};
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -497,73 +497,80 @@ static int compute_units() {
     return n[dev];
 }
 
-template <int NS, int TAPS, int MT, bool W32 = false, int NG = 2>
-static int launch_wrw_tr(ConvWrwParams &p, hipStream_t s) {
-    using G = WrwTrGeom<TAPS, MT>;
-    constexpr size_t lds = G::lds_bytes(NS, W32, NG);
-    static_assert(lds <= 160 * 1024, "one workgroup per CU");
-    static LdsLimit attr_max_e;
-    if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&convwrw_tr_kernel<NS, TAPS, MT, W32, NG>), lds, "glowtts_conv_wrw (tr)")) return rc_;
-    const int tiles = ((p.Cin + 63) / 64) * ((p.M + G::MR - 1) / G::MR);
-    const int total = p.B * ((p.T + G::CF - 1) / G::CF);
-    int splits = compute_units() / tiles;               // ONE workgroup (8 waves) per CU, one round
+// the instantiations as (NS, TAPS, MT, W32, NG): ONE list for the plan's LDS bytes and for the ladder
+#define GLOWTTS_WRW_TR_FORMS(X) \
+    X(3, 3, 4, false, 2) X(3, 3, 2, true, 2) X(3, 5, 4, false, 1) X(3, 5, 4, false, 2) X(3, 5, 2, true, 2) X(3, 5, 2, false, 2) \
+    X(2, 5, 2, false, 2) X(1, 5, 2, false, 2)
+
+// Which form a frame-packed weight gradient (dilation 1, 'same' padding, 16-byte rows: checked by the caller) takes in the plane mode
+// sn.math_wrw, and its split-K; false = not this kernel's
+bool plan_wrw_tr(const ConvWrwParams &p, const ConvSnapshot &sn, ConvPlan &plan) {
+    const int ns = sn.math_wrw, tr = sn.knob[K_WRW_TR];   // -1 unset, 0 = off, 1 = 64 x 32 tiles in the 16x16x32 form
+    if (tr == 0) return false;
+    if (p.M % 32 != 0 || (p.d2 && p.d_split % 32 != 0)) return false;
+    int mt = 2, ng = 2;
+    bool w32 = false;
+    if (p.taps == 3) {        // the text encoder's FFN convolutions (768 <-> 192 channels, T_text frames)
+        if (ns != 3 || sn.knob[K_WRW_TR3] == 0) return false;
+        if (sn.knob[K_WRW_TR3_MT] == 4 && p.M % 64 == 0) mt = 4;
+        else w32 = true;
+    } else if (p.taps == 5) {
+        // default: 64 x 64 tiles (x staged once per 64 output channels: the loop runs at 86 % of the pipe), whose 20 MB of atomics
+        // drain while the other stream's kernels run — alone it is no faster than the 64 x 32 form (61 us either way), in the step it
+        // is (16.25 -> 16.00 ms, three alternating runs).  GLOWTTS_WRW_TR_MT=2 selects 64 x 32 tiles in the 32x32x16 form with the
+        // storing waves at raised priority (A/B at B=32 / T'=400, production build: 65.7 us per back-to-back launch; 16x16x32 form
+        // 66.3; either form with the MULTIPLYING waves raised 67-69), GLOWTTS_WRW_TR=1 their 16x16x32 form
+        const bool mt2 = sn.knob[K_WRW_TR_MT] == 2, w16 = tr == 1;
+        if (ns == 3 && !mt2 && !w16 && p.M % 64 == 0 && (!p.d2 || p.d_split % 64 == 0)) {
+            mt = 4;
+            ng = sn.knob[K_WRW_TR_NG] == 1 ? 1 : 2;
+        } else {
+            w32 = ns == 3 && !w16;
+        }
+    } else {
+        // 1x1 convolutions stay on the frame-packed kernel: this one is staging-bound there (measured at B=32 / T'=400, 384 <- 192
+        // channels: 45 us as 64x32 tiles, 34 us as 64x64, against 30.5 us)
+        return false;
+    }
+    plan.family = GLOWTTS_PLAN_WRW_TR;
+    plan.ns = plan.nsa = ns; plan.mt = mt; plan.ng = ng; plan.w32 = w32; plan.frame_tile = 64; plan.block = 256 * ng;
+#define GLOWTTS_WRW_TR_LDS(NS, TAPS, MT, W32, NG) \
+    if (ns == NS && p.taps == TAPS && mt == MT && w32 == W32 && ng == NG) plan.lds_bytes = (int)WrwTrGeom<TAPS, MT>::lds_bytes(NS, W32, NG);
+    GLOWTTS_WRW_TR_FORMS(GLOWTTS_WRW_TR_LDS)
+#undef GLOWTTS_WRW_TR_LDS
+    const int tiles = ((p.Cin + 63) / 64) * ((p.M + 16 * mt - 1) / (16 * mt));
+    const int total = p.B * ((p.T + 63) / 64);
+    int splits = sn.cus / tiles;                        // ONE workgroup (8 waves) per CU, one round
     // A batch of nbatch problems shares the compute units: ONE round of workgroups for the whole batch (4 problems x 18 tiles x 3
     // splits = 216 workgroups of 75 items each at config 2) instead of one round per problem (4 x 252 workgroups of 16 items):
     // nbatch times fewer prologues, group reductions and split-K atomics per problem (82 KB per workgroup: 20.7 -> 4.4 MB per
     // problem) for 16 % of the compute units left to the other streams; 15.08 -> 14.98 ms per step (tools/ab_flags.py
     // envs=GLOWTTS_WRW5_BSPLIT:0,GLOWTTS_WRW5_BSPLIT:1; two launches of two problems x 7 splits: 15.01).  Read at every launch.
-    if (p.nbatch > 1 && knob(K_WRW5_BSPLIT) == 1 && compute_units() >= tiles * p.nbatch) {
-        const int cus = knob(K_WRW5_CUS);          // -1: every compute unit; a smaller number leaves the rest to the backward's chain
-        splits = ((cus > 0 && cus < compute_units()) ? cus : compute_units()) / (tiles * p.nbatch);
+    if (p.nbatch > 1 && sn.knob[K_WRW5_BSPLIT] == 1 && sn.cus >= tiles * p.nbatch) {
+        const int cus = sn.knob[K_WRW5_CUS];        // -1: every compute unit; a smaller number leaves the rest to the backward's chain
+        splits = ((cus > 0 && cus < sn.cus) ? cus : sn.cus) / (tiles * p.nbatch);
     }
-    if (NG == 1) splits *= knob(K_WRW_TR_NG_SPLITS);      // (one group: workgroups per CU's worth of items; 1 = same grid)
+    if (ng == 1) splits *= sn.knob[K_WRW_TR_NG_SPLITS];   // (one group: workgroups per CU's worth of items; 1 = same grid)
     if (splits > (total + 1) / 2) splits = (total + 1) / 2;      // a workgroup wants an item for each of its two groups
-    if (splits < 1) splits = 1;
-    p.nb = (total + splits - 1) / splits;
-    p.xs_pitch = knob(K_WRW_TR_PRIO);         // (tuning switch: 0 = the multiplying waves run at raised priority, 1 = nobody, 2 = the storing waves)
-    dim3 grid(tiles, 1, ((total + p.nb - 1) / p.nb) * (p.nbatch > 0 ? p.nbatch : 1));
-    hipLaunchKernelGGL((convwrw_tr_kernel<NS, TAPS, MT, W32, NG>), grid, dim3(256 * NG), lds, s, p);
-    GLOWTTS_LAUNCH_CHECK("glowtts_conv_wrw (tr)");
+    wrw_split_k(plan, tiles, total, splits);
+    return true;
 }
 
-// called by conv_wrw_split_dispatch for fp32 tensors: -1 = not handled here
-int conv_wrw_tr_dispatch(ConvWrwParams &p, int ns, hipStream_t s) {
-    const int tr = knob(K_WRW_TR);                    // -1 unset, 0 = off, 1 = 64 x 32 tiles in the 16x16x32 form
-    if (tr == 0) return -1;
-    if (p.M % 32 != 0 || (p.d2 && p.d_split % 32 != 0)) return -1;
-    if (p.taps == 3) {        // the text encoder's FFN convolutions (768 <-> 192 channels, T_text frames)
-        const bool no3 = knob(K_WRW_TR3) == 0;
-        if (ns == 3 && !no3 && knob(K_WRW_TR3_MT) == 4 && p.M % 64 == 0) return launch_wrw_tr<3, 3, 4>(p, s);
-        return (ns == 3 && !no3) ? launch_wrw_tr<3, 3, 2, true>(p, s) : -1;
+int launch_wrw_tr(ConvWrwParams &p, const ConvPlan &plan, hipStream_t s) {
+    p.xs_pitch = knob(K_WRW_TR_PRIO);         // (tuning switch: 0 = the multiplying waves run at raised priority, 1 = nobody, 2 = the storing waves)
+#define GLOWTTS_WRW_TR_LAUNCH(NS, TAPS, MT, W32, NG)                                                                  \
+    if (plan.ns == NS && plan.taps == TAPS && plan.mt == MT && (plan.w32 != 0) == W32 && plan.ng == NG) {             \
+        static_assert(WrwTrGeom<TAPS, MT>::lds_bytes(NS, W32, NG) <= 160 * 1024, "one workgroup per CU");             \
+        return launch_planned<&convwrw_tr_kernel<NS, TAPS, MT, W32, NG>>(plan, "glowtts_conv_wrw (tr)", s, p);        \
     }
-    // 1x1 convolutions stay on the frame-packed kernel: this one is staging-bound there (measured at B=32 / T'=400, 384 <- 192
-    // channels: 45 us as 64x32 tiles, 34 us as 64x64, against 30.5 us)
-    if (p.taps != 5) return -1;
-    // default: 64 x 64 tiles (x staged once per 64 output channels: the loop runs at 86 % of the pipe), whose 20 MB of atomics
-    // drain while the other stream's kernels run — alone it is no faster than the 64 x 32 form (61 us either way), in the step it
-    // is (16.25 -> 16.00 ms, three alternating runs).  GLOWTTS_WRW_TR_MT=2 selects 64 x 32 tiles in the 32x32x16 form with the
-    // storing waves at raised priority (A/B at B=32 / T'=400, production build: 65.7 us per back-to-back launch; 16x16x32 form
-    // 66.3; either form with the MULTIPLYING waves raised 67-69), GLOWTTS_WRW_TR=1 their 16x16x32 form
-    const bool mt2 = knob(K_WRW_TR_MT) == 2, w16 = tr == 1;
-    if (ns == 3 && !mt2 && !w16 && p.M % 64 == 0 && (!p.d2 || p.d_split % 64 == 0))
-        return knob(K_WRW_TR_NG) == 1 ? launch_wrw_tr<3, 5, 4, false, 1>(p, s) : launch_wrw_tr<3, 5, 4>(p, s);
-    if (ns == 3 && !w16) return launch_wrw_tr<3, 5, 2, true>(p, s);
-    if (ns == 3) return launch_wrw_tr<3, 5, 2>(p, s);
-    if (ns == 2) return launch_wrw_tr<2, 5, 2>(p, s);
-    if (ns == 1) return launch_wrw_tr<1, 5, 2>(p, s);
-    return -1;
+    GLOWTTS_WRW_TR_FORMS(GLOWTTS_WRW_TR_LAUNCH)
+#undef GLOWTTS_WRW_TR_LAUNCH
+    set_error("glowtts_conv_wrw (tr): planned a form that does not exist");
+    return 1;
 }
 
 }  // namespace glowtts
 
 #ifdef GLOWTTS_TRACE
-extern "C" int glowtts_debug_trace_read_tr(unsigned long long *host, int n_words, int clear) {
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(glowtts::g_trace), (size_t)n_words * 8);
-    if (e != hipSuccess) return (int)e;
-    if (clear) {
-        static unsigned long long zeros[8192 * 16];
-        e = hipMemcpyToSymbol(HIP_SYMBOL(glowtts::g_trace), zeros, sizeof(zeros));
-    }
-    return (int)e;
-}
+extern "C" int glowtts_debug_trace_read_tr(unsigned long long *host, int n_words, int clear) { return glowtts::trace_read(host, n_words, clear); }
 #endif

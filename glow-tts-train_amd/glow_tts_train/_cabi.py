@@ -8,6 +8,7 @@ name — a guessed type would hand a kernel shifted arguments:
     int                                                       -> c_int
     float                                                     -> c_float
     long, long long, unsigned long long, int64_t              -> c_int64
+    int32_t (struct fields the library writes)                -> c_int32
 """
 import ctypes
 import os
@@ -17,7 +18,8 @@ HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.pa
                            "include", "glowtts_hip.h")
 
 _SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "long": ctypes.c_int64, "long long": ctypes.c_int64,
-            "unsigned long long": ctypes.c_int64, "int64_t": ctypes.c_int64, "glowtts_stream_t": ctypes.c_void_p}
+            "unsigned long long": ctypes.c_int64, "int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32,
+            "glowtts_stream_t": ctypes.c_void_p}
 
 
 class HipLibraryMissing(RuntimeError):

@@ -36,6 +36,7 @@ WnLayer = _STRUCTS["glowtts_wn_layer"]
 Wrw1Problem = _STRUCTS["glowtts_wrw1_problem"]
 FlowBlock = _STRUCTS["glowtts_flow_block"]
 EncLayer = _STRUCTS["glowtts_enc_layer"]
+ConvPlan = _STRUCTS["glowtts_conv_plan"]          # written BY the library: glowtts_conv_plan_next
 
 EXPORTED_SYMBOLS = sorted(_FUNCTIONS)
 

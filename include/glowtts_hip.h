@@ -100,6 +100,52 @@ int glowtts_abi_version(void);
 int glowtts_set_knob(const char *name, int value);
 int glowtts_get_knob(const char *name, int *value);
 
+/* ---- what would this convolution launch?  (no reference counterpart) ----------------------------------------------------------
+ * Every entry point of the convolution family (glowtts_conv_fwd / _fwd_io / _fwd_act, _conv_gate_fwd, _conv_res_skip_fwd,
+ * _conv_gate_bwd and their _io forms, glowtts_conv_wrw / _wrw2 / _wrw_batch / _wrw_planes) checks its arguments, DECIDES what to
+ * launch — a pure host function of the arguments, the arithmetic modes, the planes bound to the calling thread and the tuning
+ * switches above (csrc/conv_plan.hpp) — and then launches the decision.  glowtts_conv_plan_next(out) arms the CALLING THREAD: the
+ * next such decision on it is written to *out, and that call returns 0 without launching anything and without touching the device
+ * (so it works on a machine without a GPU, with any integers for addresses; only their alignment is looked at).  Argument errors
+ * are reported exactly as without arming; whether the thread is still armed after one is unspecified: NULL disarms.  A stacked
+ * executor (glowtts_wn_fwd, glowtts_flow_block_fwd, ..) consumes the arming at its FIRST inner convolution and launches the rest.
+ *   family       : GLOWTTS_PLAN_* below; GLOWTTS_PLAN_NONE with launches = 0: the call had nothing to launch (B T = 0)
+ *   epi          : forward-type families: 0 plain, 1 gate, 2 res/skip, 3 res/skip of the last layer, 4 addend, 5 gate backward
+ *   ns, nsa, iob : bf16 planes per activation / per weight (0 = fp32 MFMA), bf16 tensors in HBM (1 = all, 2 = x only)
+ *   rows         : output rows per workgroup (forward-type) / 64, the input channels per workgroup (weight gradients)
+ *   frame_tile   : frames per workgroup tile (forward-type) / per chunk (weight gradients)
+ *   taps         : compile-time taps of the kernel, 0 = a run-time loop
+ *   mt, ng, w32  : weight gradients: 16-row output-gradient tiles per workgroup tile; wave groups per workgroup and the
+ *                  32x32x16 MFMA form (transposed-read kernel)
+ *   nb           : weight gradients: chunks (generic kernel: utterances) per workgroup of the split contraction
+ *   nbatch       : problems in the launch (0 = a single problem)
+ *   launches     : kernel launches the CALL would have made: 2 for the generic weight gradient with a bias gradient (its row
+ *                  sums are a second kernel), the total over the groups for glowtts_conv_wrw_batch (the other fields then
+ *                  describe its first launch) */
+#define GLOWTTS_PLAN_NONE 0
+#define GLOWTTS_PLAN_GENERIC 1     /* fp32 MFMA, any shape */
+#define GLOWTTS_PLAN_PIPE 2        /* fp32 MFMA, pipelined: 1 / 3 / 5 taps, 16-byte rows */
+#define GLOWTTS_PLAN_SPLIT 3       /* bf16-plane arithmetic on fp32 tensors */
+#define GLOWTTS_PLAN_BF16IO 4      /* bf16 tensors */
+#define GLOWTTS_PLAN_WINO_GATE 5   /* Winograd F(4, 5) gated in-conv */
+#define GLOWTTS_PLAN_WINO_BWD 6    /* ... and its backward-data (falls back to the direct plan where its workspace cannot be had) */
+#define GLOWTTS_PLAN_WRW_GENERIC 7 /* weight gradients: any shape (+ row sums) */
+#define GLOWTTS_PLAN_WRW_PIPE 8    /* ... pipelined, any dilation / padding */
+#define GLOWTTS_PLAN_WRW_FP 9      /* ... frame-packed, fp32 MFMA */
+#define GLOWTTS_PLAN_WRW_SPLIT 10  /* ... frame-packed, bf16 planes */
+#define GLOWTTS_PLAN_WRW_PLANES 11 /* ... frame-packed, operands given as planes */
+#define GLOWTTS_PLAN_WRW_TR 12     /* ... frame-major images, transposing LDS reads */
+typedef struct glowtts_conv_plan {
+    int32_t family, epi;
+    int32_t ns, nsa, iob;
+    int32_t rows, frame_tile, taps;
+    int32_t vec_epilogue, wg_order, xp_pitch;
+    int32_t mt, ng, w32, nb, nbatch;
+    int32_t grid_x, grid_y, grid_z, block, lds_bytes;
+    int32_t launches;
+} glowtts_conv_plan;
+int glowtts_conv_plan_next(glowtts_conv_plan *out);
+
 /* ---- monotonic alignment search ----------------------------------------------------------------------------
  * replaces maximum_path_c / maximum_path_each (monotonic_align/core.pyx:9-45) and the D2H/H2D round trip of its
  * wrapper (monotonic_align/__init__.py:11-21).

@@ -138,7 +138,7 @@ def test_flow_stack_bf16_tensors_track_fp32(G, mode, b, t, blocks, p_drop):
 @pytest.mark.parametrize("mels", [64, 128])
 def test_flow_stack_bf16_other_mel_widths(G, mode, mels):
     """Squeezed C = 128 / 256 (64 / 128 mels): the end conv (M = C) and the start conv's input gradient (M = C/2) fall on
-    dispatch_convgemm's 128-row preference, for which the 1x1 bf16-tensor kernels are not instantiated: they
+    rows_big's 128-row preference (csrc/conv_plan.hpp), for which the 1x1 bf16-tensor kernels are not instantiated: they
     must run on the 64-row form — the block runs with bf16 tensors and tracks the fp32 path, no 'no kernel for epilogue'."""
     b, t, blocks = 2, 96, 2
     dec = _decoder(G, blocks, mels=mels)

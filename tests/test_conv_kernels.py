@@ -61,10 +61,13 @@ Two kinds of input.
          afterwards.  Each GPU test prints its figures (-s).
 
 Shapes: FWD, GATE, RESSKIP, GATEBWD, WRW, WRW2, ROWSUM below: each row is the smallest shape that takes a branch of the launchers
-and says which; _fwd_mirror / _wrw_mirror restate the launchers' predicates (line references into csrc/) and label every row;
-test_every_branch_is_reached asserts that the labels reached are exactly the EXPECT_* lists, so a shape that silently stops
-reaching its branch fails on the CPU.  B <= 8, channels <= 384, T <= 192 throughout.
+and says which; _fwd_mirror / _wrw_mirror restate the planners' rules (csrc/conv_plan.hpp, plan_conv_fwd / plan_conv_wrw) and label
+every row; test_every_branch_is_reached asserts that the labels reached are exactly the EXPECT_* lists, and
+test_plans_agree_with_the_mirrors asks the library itself (glowtts_conv_plan_next: no GPU needed) what it would launch for every
+row, so neither a shape that silently stops reaching its branch nor a rule moved in the C++ passes on the CPU.  B <= 8,
+channels <= 384, T <= 192 throughout.
 """
+import ctypes
 import functools
 import math
 import re
@@ -388,23 +391,23 @@ FWD = [
 
 
 def _fwd_mirror(c):
-    """The decisions of dispatch_convgemm for conv_fwd / conv_fwd_act (csrc/convgemm.hip:882-915), launch_convgemm_wd's vec_epilogue
-    (:858-860) and dispatch_split_ns (csrc/convgemm_split.hip:935-964) -> namespace with the labels of the case."""
+    """The decisions of plan_conv_fwd for conv_fwd / conv_fwd_act (csrc/convgemm.hip) with the rules of csrc/conv_plan.hpp and
+    conv_split_has (csrc/convgemm_split.hip) -> namespace with the labels of the case."""
     halo = (c.taps - 1) * c.dil
-    x_aligned, x_bs_ok = c.mis != "x", not c.x_bs_odd                                     # convgemm.hip:886
-    pipe_ok = c.T % 4 == 0 and x_aligned and x_bs_ok and halo <= 12                       # :886-888 (the mask is always aligned here)
-    wd = pipe_ok and c.taps in (1, 3, 5)                                                  # dispatch_taps :872-879
-    n5 = c.T % 80 == 0 or (c.T % 64 != 0 and -(-c.T // 80) * 80 < -(-c.T // 64) * 64)     # :884
-    big = c.M % 128 == 0 or c.M > 192                                                     # :885
+    x_aligned, x_bs_ok = c.mis != "x", not c.x_bs_odd                                     # fwd_pipe_ok
+    pipe_ok = c.T % 4 == 0 and x_aligned and x_bs_ok and halo <= 12                       # fwd_pipe_ok (the mask is always aligned here)
+    wd = pipe_ok and c.taps in (1, 3, 5)                                                  # plan_conv_fwd: PIPE or GENERIC
+    n5 = c.T % 80 == 0 or (c.T % 64 != 0 and -(-c.T // 80) * 80 < -(-c.T // 64) * 64)     # frames80_fwd
+    big = c.M % 128 == 0 or c.M > 192                                                     # rows_big
     epi = "ADD" if c.addend else "PLAIN"
     use32 = False
-    if epi == "PLAIN" and pipe_ok:                                                        # :893-906
+    if epi == "PLAIN" and pipe_ok:                                                        # fwd_use32
         wg5 = -(-c.T // 80) * c.B * -(-c.M // (128 if big else 64))
         t32 = -(-c.T // 32) * 32
         use32 = (wg5 < 380 and t32 * 10 <= c.T * 11) or (c.taps == 1 and t32 * 10 <= c.T * 11)
-    nct = 2 if use32 else (5 if n5 else 4)                                                # :907
-    vec = wd and c.mis not in ("y", "addend") and not c.y_bs_odd                          # :858-860
-    split = None                                                                          # convgemm_split.hip:1046-1055, 935-964
+    nct = 2 if use32 else (5 if n5 else 4)                                                # plan.frame_tile
+    vec = wd and c.mis not in ("y", "addend") and not c.y_bs_odd                          # vec_epilogue
+    split = None                                                                          # plan_conv_fwd: SPLIT; conv_split_has
     if pipe_ok:
         if c.taps == 5 and not big and nct != 2:
             split = f"{epi}5/64"
@@ -440,7 +443,8 @@ def _fwd_mirror(c):
         L |= {n for n in ("relu", "drop", "gate_pos") if getattr(c, n) and sum(map(bool, (c.relu, c.drop, c.gate_pos))) == 1}
     L |= {"bwd-data"} if c.bwd else set()
     L.add("split:" + (split or "none"))
-    return types.SimpleNamespace(pipe_ok=pipe_ok, wd=wd, n5=n5, big=big, use32=use32, vec=vec, split=split, labels=L)
+    wg5 = -(-c.T // 80) * c.B * -(-c.M // rows)
+    return types.SimpleNamespace(pipe_ok=pipe_ok, wd=wd, n5=n5, big=big, use32=use32, vec=vec, split=split, labels=L, wg5=wg5)
 
 
 EXPECT_FWD = {
@@ -499,7 +503,8 @@ def _fwd_ref(c, I, dt):
     return y, s
 
 
-def _fwd_launch(G, c, I, mode):
+def _fwd_launch(G, c, I, mode, arm=None):
+    """arm: a ConvPlan — glowtts_conv_plan_next(arm) right before the call, which then must launch nothing."""
     D = _Dev()
     B, Cin, M, T = c.B, c.Cin, c.M, c.T
     gen = _gen(B, Cin, M, T)
@@ -522,6 +527,8 @@ def _fwd_launch(G, c, I, mode):
     args = [x_ptr, x_bs, wp_ptr, D.inp("bias", I.bias), D.inp("mask", I.mask) if any_mask else None, a_ptr, a_bs, y_ptr, y_bs,
             B, Cin, M, T, c.taps, c.dil, c.pad, c.mask_in, c.mask_out, c.mask_add]
     _set_mode(G, mode, wp_ptr, I.wp.numel())
+    if arm is not None:
+        assert G.lib.glowtts_conv_plan_next(ctypes.byref(arm)) == 0
     if c.act:
         G.hip.call("glowtts_conv_fwd_act", *args, c.relu, D.inp("drop", I.drop), I.drop_scale, D.inp("gate_pos", I.gate_pos), I.gate_scale)
     else:
@@ -579,8 +586,8 @@ EXPECT_GATE = {"H20", "H96", "H192", "taps3", "taps5", "dil2", "generic:T%4", "p
 
 
 def _gate_mirror(c):
-    pipe_ok = c.T % 4 == 0 and (c.taps - 1) * c.dil <= 12 and c.H % 4 == 0                # convgemm.hip:886-888
-    split = "GATE5" if pipe_ok and c.taps == 5 else None                                  # convgemm_split.hip:940 (EPI_GATE is always `big`)
+    pipe_ok = c.T % 4 == 0 and (c.taps - 1) * c.dil <= 12 and c.H % 4 == 0                # fwd_pipe_ok
+    split = "GATE5" if pipe_ok and c.taps == 5 else None                                  # conv_split_has (EPI_GATE is always `big`)
     L = {f"H{c.H}", f"taps{c.taps}", "pipe" if pipe_ok and c.taps in (1, 3, 5) else "generic:T%4", "split:" + (split or "none")}
     L |= {"dil2"} if c.dil == 2 else set()
     L |= {"cond+drop"} if c.cond and c.drop else {"cond"} if c.cond else {"drop"} if c.drop else set()
@@ -691,9 +698,9 @@ EXPECT_RESSKIP = {"H20", "H96", "H192", "last0", "last1", "skip-null", "alias", 
 
 def _rs_mirror(c):
     M = c.H if c.last else 2 * c.H
-    big = M % 128 == 0 or M > 192                                                         # convgemm.hip:885
+    big = M % 128 == 0 or M > 192                                                         # rows_big
     pipe_ok = c.T % 4 == 0
-    split = None                                                                          # convgemm_split.hip:941-942
+    split = None                                                                          # conv_split_has
     if pipe_ok and c.last and not big:
         split = "RESSKIP_LAST/64"
     elif pipe_ok and not c.last and big:
@@ -795,9 +802,9 @@ EXPECT_GATEBWD = {"H20", "H96", "H192", "M_rs=2H", "M_rs=H", "drop", "two-source
 
 
 def _gb_mirror(c):
-    big = c.H % 128 == 0 or c.H > 192                                                     # convgemm.hip:885 (M = H)
+    big = c.H % 128 == 0 or c.H > 192                                                     # rows_big (M = H)
     pipe_ok = c.T % 4 == 0
-    split = "GATEBWD/64" if pipe_ok and not big else None                                 # convgemm_split.hip:943
+    split = "GATEBWD/64" if pipe_ok and not big else None                                 # conv_split_has
     L = {f"H{c.H}", "M_rs=2H" if c.M_rs == 2 * c.H else "M_rs=H", "pipe" if pipe_ok else "generic:T%4", "split:" + (split or "none")}
     L |= {"drop"} if c.drop else set()
     L |= {"two-source"} if c.two else set()
@@ -921,37 +928,39 @@ EXPECT_WRW2 = {"d_split64", "d_split128", "fp<1,64>", "fp<5,80,MT2>", "fp<5,64,M
 
 
 def _wrw_mirror(c):
-    """glowtts_conv_wrw / _wrw2 (csrc/convgemm.hip:1104-1167), launch_wrw_fp / _pipe (:917-962), conv_wrw_split_dispatch
-    (csrc/convgemm_split.hip:1013-1031) and conv_wrw_tr_dispatch (csrc/convwrw_tr.hip:530-555) at the default switches."""
-    halo, L = (c.taps - 1) * c.dil, set()
-    pipe_ok = c.T % 4 == 0 and halo <= 12                                                 # convgemm.hip:1135-1136 (all tensors aligned here)
+    """plan_conv_wrw (csrc/convgemm.hip) for glowtts_conv_wrw / _wrw2 with the rules of csrc/conv_plan.hpp and plan_wrw_tr
+    (csrc/convwrw_tr.hip) at the default switches."""
+    halo, L, geo = (c.taps - 1) * c.dil, set(), None
+    pipe_ok = c.T % 4 == 0 and halo <= 12                                                 # wrw_pipe_ok (all tensors aligned here)
     m15 = "native"
     if pipe_ok and c.taps in (1, 3, 5):
-        if c.dil == 1 and c.pad == (c.taps - 1) // 2:                                     # :1139
-            n5 = c.T % 80 == 0 or -(-c.T // 80) * 80 <= -(-c.T // 64) * 64               # :1141
+        if c.dil == 1 and c.pad == (c.taps - 1) // 2:                                     # wrw_frame_packed
+            n5 = c.T % 80 == 0 or -(-c.T // 80) * 80 <= -(-c.T // 64) * 64               # frames80_wrw
             ct = 80 if n5 else 64
-            mt = 2 if c.taps == 5 and c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) else 4     # :941-943
+            mt = 2 if c.taps == 5 and c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) else 4     # wrw_fp_mt
             L.add(f"fp<{c.taps},{ct}" + (f",MT{mt}>" if c.taps == 5 else ">"))
-            tiles, total = -(-c.Cin // 64) * -(-c.M // (16 * mt)), c.B * -(-c.T // ct)   # :925-930
+            tiles, total = -(-c.Cin // 64) * -(-c.M // (16 * mt)), c.B * -(-c.T // ct)   # wrw_split_k
             splits = max(1, min((768 if mt <= 2 else 512) // tiles, total))
             nb, nct = -(-total // splits), -(-c.T // ct)
+            geo = (tiles, 1, -(-total // nb), nb)
             spans = any(s // nct != (min(total, s + nb) - 1) // nct for s in range(0, total, nb))
             if spans and total % nb:
                 L.add("spans-utterances+short-last")
-            if c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) and c.taps == 3:  # convwrw_tr.hip:533-538
+            if c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) and c.taps == 3:  # plan_wrw_tr
                 m15 = "tr<3>"
-            elif c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) and c.taps == 5:    # :541-550
+            elif c.M % 32 == 0 and (not c.d_split or c.d_split % 32 == 0) and c.taps == 5:    # plan_wrw_tr
                 m15 = "tr<5,64x64>" if c.M % 64 == 0 and (not c.d_split or c.d_split % 64 == 0) else "tr<5,64x32>"
-            elif c.taps == 1:                                                             # convgemm_split.hip:1018
+            elif c.taps == 1:                                                             # plan_conv_wrw: WRW_SPLIT
                 m15 = "split<1>"
         else:
-            L.add(f"pipe<{c.taps},{40 if c.T % 40 == 0 else 32}>")                        # convgemm.hip:1146-1149
+            L.add(f"pipe<{c.taps},{40 if c.T % 40 == 0 else 32}>")                        # plan_conv_wrw: WRW_PIPE
             if c.dil == 1:
                 L.add("pad-not-same")
     else:
-        tiles = -(-c.Cin // 64) * -(-c.M // 128) * c.taps                                 # :1151-1155
+        tiles = -(-c.Cin // 64) * -(-c.M // 128) * c.taps                                 # plan_conv_wrw: WRW_GENERIC
         splits = max(1, min(-(-768 // tiles), c.B))
         nb = -(-c.B // splits)
+        geo = (tiles // c.taps, c.taps, -(-c.B // nb), nb)
         L.add("generic")
         if c.B % nb:
             L.add("generic:B-not-multiple-of-split")
@@ -965,7 +974,7 @@ def _wrw_mirror(c):
     L |= {"d-slice"} if c.d_slice else set()
     L.add("dbias" if c.dbias else "dbias-null")
     L |= {f"d_split{c.d_split}"} if c.d_split else set()
-    return types.SimpleNamespace(labels=L, m15=m15)
+    return types.SimpleNamespace(labels=L, m15=m15, geo=geo)
 
 
 @functools.lru_cache(maxsize=None)
@@ -1256,6 +1265,315 @@ def test_every_branch_is_reached():
     span = next(c for c in WRW if c.name == "f5-span")
     assert "spans-utterances+short-last" in _wrw_mirror(span).labels
     assert {(c.M, c.T > 1024 or c.M > 1024) for c in ROWSUM} >= {(1, False), (1030, True)}
+
+
+# ---- what the library itself says it would launch (glowtts_conv_plan_next): no GPU, dummy addresses --------------------------------
+_EPI = {0: "PLAIN", 1: "GATE", 2: "RESSKIP", 3: "RESSKIP_LAST", 4: "ADD", 5: "GATEBWD"}
+_WP_FLOATS = 1 << 20          # floats of the dummy packed-weight buffer that the dummy planes are bound to
+
+
+class _Addr:
+    """16-byte aligned integers that stand for device buffers (a planned call looks at their alignment only); mis: 4 bytes off."""
+
+    def __init__(self):
+        self.next = 1 << 24
+
+    def __call__(self, mis=False):
+        self.next += 1 << 24
+        return self.next + (4 if mis else 0)
+
+
+@pytest.fixture()
+def P():
+    """The library with the plan constants; restores the arithmetic mode, the plane binding, the arming and every tuning switch."""
+    from glow_tts_train import _hip
+
+    lib = _hip.load()
+    before = lib.glowtts_conv_math(-1)
+    knobs = {}
+    ns = types.SimpleNamespace(lib=lib, hip=_hip, knobs=knobs, **{k[len("GLOWTTS_PLAN_"):]: v for k, v in _hip.CONSTANTS.items()
+                                                                 if k.startswith("GLOWTTS_PLAN_")})
+
+    def set_knob(name, value):
+        if name not in knobs:
+            v = ctypes.c_int()
+            assert lib.glowtts_get_knob(name.encode(), ctypes.byref(v)) == 0
+            knobs[name] = v.value
+        assert lib.glowtts_set_knob(name.encode(), value) == 0
+
+    ns.set_knob = set_knob
+    yield ns
+    for name, value in knobs.items():
+        assert lib.glowtts_set_knob(name.encode(), value) == 0
+    lib.glowtts_conv_plan_next(None)
+    lib.glowtts_conv_bind_planes(None, 0, None)
+    assert lib.glowtts_conv_math(before) == 0
+
+
+def _planned(P, mode, name, *args, wp=None):
+    """The plan of the entry point `name` at these arguments in arithmetic `mode` (with dummy planes bound to wp in a plane mode)."""
+    lib = P.lib
+    assert lib.glowtts_conv_math(mode) == 0
+    lib.glowtts_conv_bind_planes(None, 0, None)
+    if (mode & 3) and wp is not None:
+        assert lib.glowtts_conv_bind_planes(wp, _WP_FLOATS, 1 << 40) == 0
+    plan = P.hip.ConvPlan()
+    assert lib.glowtts_conv_plan_next(ctypes.byref(plan)) == 0
+    rc = getattr(lib, name)(*args, None)
+    lib.glowtts_conv_plan_next(None)
+    assert rc == 0, (name, lib.glowtts_last_error())
+    assert plan.family != P.NONE and plan.launches >= 1 and plan.lds_bytes <= 160 * 1024 and plan.grid_x * plan.grid_y * plan.grid_z >= 1
+    return plan
+
+
+def _fwd_plan(P, c, mode):
+    A, B, Cin, M, T = _Addr(), c.B, c.Cin, c.M, c.T
+    x_bs = 2 * Cin * T if c.x_slice else Cin * T + (2 if c.x_bs_odd else 0)
+    x = A(c.mis == "x") + (4 * Cin * T if c.x_slice else 0)
+    a, a_bs = (A(c.mis == "addend"), 2 * M * T if c.a_slice else M * T) if c.addend else (None, 0)
+    y_bs = 2 * M * T if c.y_slice else M * T + (2 if c.y_bs_odd else 0)
+    y = A(c.mis == "y") + (4 * M * T if c.y_slice else 0)
+    wp = A()
+    args = [x, x_bs, wp, A(), A() if (c.mask_in or c.mask_out or c.mask_add) else None, a, a_bs, y, y_bs, B, Cin, M, T, c.taps, c.dil, c.pad,
+            c.mask_in, c.mask_out, c.mask_add]
+    if c.act:
+        return _planned(P, mode, "glowtts_conv_fwd_act", *args, c.relu, A() if c.drop else None, 2.0, A() if c.gate_pos else None, 2.0, wp=wp)
+    return _planned(P, mode, "glowtts_conv_fwd", *args, wp=wp)
+
+
+def _gate_plan(P, c, mode):
+    A = _Addr()
+    wp = A()
+    return _planned(P, mode, "glowtts_conv_gate_fwd", A(), wp, A(), A() if c.cond else None, A() if c.drop else None, 2.0, A(),
+                    None if c.ts_null else A(), c.B, c.H, c.T, c.taps, c.dil, c.pad, wp=wp)
+
+
+def _rs_plan(P, c, mode):
+    A = _Addr()
+    wp = A()
+    skip = None if c.skip_null else A()
+    return _planned(P, mode, "glowtts_conv_res_skip_fwd", A(), wp, A(), A(), None if c.last and c.xout_null else A(), skip,
+                    None if c.xout_null else A(), skip if c.alias else A(), c.B, c.H, c.T, c.last, wp=wp)
+
+
+def _gb_plan(P, c, mode):
+    A = _Addr()
+    wp = A()
+    return _planned(P, mode, "glowtts_conv_gate_bwd", A(), A() if c.two else None, wp, A(), A() if c.drop else None, 2.0, A(), c.B, c.M_rs,
+                    c.H, c.T, wp=wp)
+
+
+def _wrw_plan(P, c, mode):
+    A, B, Cin, M, T = _Addr(), c.B, c.Cin, c.M, c.T
+    x, x_bs = A() + (4 * Cin * T if c.x_slice else 0), (2 if c.x_slice else 1) * Cin * T
+    dbias = A() if c.dbias else None
+    if c.d_split:
+        S = c.d_split
+        return _planned(P, mode, "glowtts_conv_wrw2", x, x_bs, A(), S * T, A(), (M - S) * T, S, A(), dbias, B, Cin, M, T, c.taps, c.dil, c.pad)
+    return _planned(P, mode, "glowtts_conv_wrw", x, x_bs, A(), (2 if c.d_slice else 1) * M * T, A() if c.mask else None,
+                    A() if c.mask_x else None, A(), dbias, B, Cin, M, T, c.taps, c.dil, c.pad)
+
+
+def _wrw_label(P, plan):
+    """The label of _wrw_mirror that a weight-gradient plan stands for."""
+    if plan.family == P.WRW_GENERIC:
+        return "generic"
+    if plan.family == P.WRW_PIPE:
+        return f"pipe<{plan.taps},{plan.frame_tile}>"
+    if plan.family == P.WRW_FP:
+        return f"fp<{plan.taps},{plan.frame_tile}" + (f",MT{plan.mt}>" if plan.taps == 5 else ">")
+    if plan.family == P.WRW_TR:
+        return "tr<3>" if plan.taps == 3 else f"tr<5,64x{16 * plan.mt}>"
+    assert plan.family == P.WRW_SPLIT, plan.family
+    return f"split<{plan.taps}>"
+
+
+# Rows at the edges of the rules that the shape tables (B <= 8, T <= 192) cannot reach; planned on the CPU only.  T = 300 and 304 round
+# to 320 frames with 80- and with 64-frame tiles: the forward-type rule (frames80_fwd) takes 64 there, the weight-gradient rule
+# (frames80_wrw) 80 — as found, and pinned here.  38 x 2 x 5 = 380 tiles of 128 rows x 80 frames is the first grid that keeps its
+# 80-frame tiles (fwd_use32: fewer than 380 workgroups take 32-frame tiles).
+EDGE_FWD = [_fwd("edge-T300", "T = 300, addend (no 32-frame tiles): 64-frame tiles", 16, 36, 300, 3, addend=True),
+            _fwd("edge-T304", "T = 304: the same tie", 16, 36, 304, 3, addend=True),
+            _fwd("edge-T320", "T = 320: 80-frame tiles", 16, 36, 320, 3, addend=True),
+            _fwd("edge-wg370", "370 tiles of 80 frames: 32-frame tiles", 16, 640, 160, 3, B=37),
+            _fwd("edge-wg380", "380 tiles of 80 frames: they stay", 16, 640, 160, 3, B=38)]
+EDGE_WRW = [_wr("edge-T300", "T = 300: 80-frame chunks", 3, 20, 36, 300, 1), _wr("edge-T304", "T = 304: 80-frame chunks", 3, 20, 36, 304, 1),
+            _wr("edge-T256", "T = 256: 64-frame chunks", 3, 20, 36, 256, 1)]
+
+
+def _fwd_type_tables():
+    """(table, mirror, planner, the mirror's `split` label of a bf16-plane plan) of the four forward-type tables."""
+    return ((FWD + EDGE_FWD, _fwd_mirror, _fwd_plan, lambda p: "PLAIN3/32f" if p.frame_tile == 32 else f"{_EPI[p.epi]}{p.taps}/{p.rows}"),
+            (GATE, _gate_mirror, _gate_plan, lambda p: f"{_EPI[p.epi]}{p.taps}"),
+            (RESSKIP, _rs_mirror, _rs_plan, lambda p: f"{_EPI[p.epi]}/{p.rows}"),
+            (GATEBWD, _gb_mirror, _gb_plan, lambda p: f"{_EPI[p.epi]}/{p.rows}"))
+
+
+def test_plans_agree_with_the_mirrors(P):
+    """For every row of FWD, GATE, RESSKIP, GATEBWD, WRW and WRW2, natively and in mode 15, the row's real entry point is asked what it
+    would launch (glowtts_conv_plan_next; integer dummy addresses with the row's alignment): family, rows, frame tile, vector
+    epilogue, bf16-plane form, weight-gradient form, nb, grid and launch count must be what the mirror derived.  A rule moved in
+    csrc/conv_plan.hpp or in a planner without the mirror (or the other way round) fails here, on a named row."""
+    for table, mirror, planner, split_label in _fwd_type_tables():
+        for c in table:
+            mir = mirror(c)
+            generic = any(l.startswith("generic:") for l in mir.labels)
+            for mode in MODES:
+                plan, what = planner(P, c, mode), f"{c.name} mode {mode}"
+                if mode == 15 and mir.split is not None:
+                    assert (plan.family, plan.ns, plan.nsa, plan.iob) == (P.SPLIT, 3, 3, 0), what
+                    assert split_label(plan) == mir.split, (what, split_label(plan), mir.split)
+                else:
+                    assert plan.family == (P.GENERIC if generic else P.PIPE) and plan.ns == 0, (what, plan.family)
+                assert plan.taps == (0 if generic else c.taps if hasattr(c, "taps") else 1), what
+                assert (plan.block, plan.grid_z, plan.launches, plan.nbatch) == (256, 1, 1, 0), what
+                if mirror is _fwd_mirror:
+                    nt = 32 if mir.use32 else 80 if mir.n5 else 64
+                    assert plan.epi == (4 if c.addend else 0), what
+                    assert (plan.rows, plan.frame_tile, plan.vec_epilogue) == (128 if mir.big else 64, nt, int(mir.vec)), \
+                        (what, plan.rows, plan.frame_tile, plan.vec_epilogue)
+                    assert {f"rows{plan.rows}", f"nt{plan.frame_tile}"} <= mir.labels, what
+                    assert (plan.grid_x, plan.grid_y) == (c.B * -(-c.T // nt), -(-c.M // plan.rows)), what
+                    if nt == 80:
+                        assert plan.grid_x * plan.grid_y == mir.wg5, what
+                    if generic:
+                        assert plan.xp_pitch % 32 == 16 and 0 <= plan.xp_pitch - (nt + (c.taps - 1) * c.dil) < 32, what
+                else:
+                    M = 2 * c.H if table is GATE else (c.H if c.last else 2 * c.H) if table is RESSKIP else c.H
+                    rows = 128 if table is GATE or M % 128 == 0 or M > 192 else 64
+                    assert plan.epi == {id(GATE): 1, id(GATEBWD): 5}.get(id(table), 3 if getattr(c, "last", 0) else 2), what
+                    assert plan.rows == rows and plan.frame_tile == (80 if c.T % 80 == 0 else 64), (what, plan.rows, plan.frame_tile)
+                    assert plan.grid_y == (-(-c.H // 64) if table is GATE else -(-M // rows)), what
+                    assert plan.vec_epilogue == int(not generic), what
+    assert [(c.name, _fwd_mirror(c).use32, _fwd_mirror(c).n5) for c in EDGE_FWD] == [
+        ("edge-T300", False, False), ("edge-T304", False, False), ("edge-T320", False, True), ("edge-wg370", True, True), ("edge-wg380", False, True)]
+    assert [sorted(l for l in _wrw_mirror(c).labels if l.startswith("fp<")) for c in EDGE_WRW] == [["fp<1,80>"], ["fp<1,80>"], ["fp<1,64>"]]
+    for table in (WRW + EDGE_WRW, WRW2):
+        for c in table:
+            mir = _wrw_mirror(c)
+            native = _wrw_plan(P, c, 0)
+            label = _wrw_label(P, native)
+            assert label in mir.labels and native.ns == 0, (c.name, label, sorted(mir.labels))
+            assert native.launches == (2 if "generic:rowsum" in mir.labels else 1), c.name
+            if mir.geo is not None:
+                assert (native.grid_x, native.grid_y, native.grid_z, native.nb) == mir.geo, (c.name, mir.geo)
+            assert native.block == 256 and native.nbatch == 0 and native.rows == 64, c.name
+            m15 = _wrw_plan(P, c, 15)
+            if mir.m15 == "native":
+                assert [getattr(m15, f) for f, _ in m15._fields_] == [getattr(native, f) for f, _ in native._fields_], c.name
+            else:
+                assert _wrw_label(P, m15) == mir.m15 and m15.ns == 3, (c.name, _wrw_label(P, m15), mir.m15)
+                assert m15.block == (512 if m15.family == P.WRW_TR else 256), c.name
+
+
+# What the tuning switches promise (include/glowtts_hip.h, csrc/conv_plan.hpp, csrc/convwrw_tr.hip) at their non-default values: the
+# mirrors model the defaults only.  (switch, value, what a mode-15 weight-gradient plan of a row with the default label `was` becomes.)
+_TR = lambda mt, w32, ng=2: ("WRW_TR", mt, w32, ng)
+KNOB_EXPECT = [
+    ("WRW_TR", 0, {"tr<5,64x64>": ("WRW_SPLIT", 2, 0, 0), "tr<5,64x32>": ("WRW_SPLIT", 2, 0, 0), "tr<3>": ("WRW_FP", 4, 0, 0)}),
+    ("WRW_TR", 1, {"tr<5,64x64>": _TR(2, 0), "tr<5,64x32>": _TR(2, 0), "tr<3>": _TR(2, 1)}),
+    ("WRW_TR_MT", 2, {"tr<5,64x64>": _TR(2, 1), "tr<5,64x32>": _TR(2, 1), "tr<3>": _TR(2, 1)}),
+    ("WRW_TR3", 0, {"tr<5,64x64>": _TR(4, 0), "tr<5,64x32>": _TR(2, 1), "tr<3>": ("WRW_FP", 4, 0, 0)}),
+    ("WRW_TR3_MT", 4, {"tr<5,64x64>": _TR(4, 0), "tr<5,64x32>": _TR(2, 1), "tr<3>": _TR(2, 1), "tr<3>/M64": _TR(4, 0)}),
+    ("WRW_TR_NG", 1, {"tr<5,64x64>": _TR(4, 0, 1), "tr<5,64x32>": _TR(2, 1), "tr<3>": _TR(2, 1)}),
+]
+# shapes the tables do not hold: a 3-tap weight gradient with M % 64 == 0 (GLOWTTS_WRW_TR3_MT), and a plain 1x1 convolution whose
+# 80-frame grid is past the small-grid rule (480 tiles), so that only GLOWTTS_CONV32_1X1 gives it 32-frame tiles
+KNOB_WRW3_M64 = _wr("k-f3-M64", "3 taps, M = 64", 3, 70, 64, 80, 3)
+KNOB_1X1 = _fwd("k-1x1", "the coupling's end conv at the benchmark's size", 192, 160, 400, 1, B=32)
+
+
+def test_plans_follow_the_tuning_switches(P):
+    """The rows again with each launch-geometry switch at its non-default value: the default plan first (the mirror's), then the
+    family / tile the header promises for the switch.  Every switch is restored afterwards (fixture)."""
+    rows = [(c, _wrw_mirror(c).m15) for c in WRW + WRW2] + [(KNOB_WRW3_M64, "tr<3>/M64")]
+    assert {m for _, m in rows} >= {"tr<5,64x64>", "tr<5,64x32>", "tr<3>", "tr<3>/M64", "split<1>", "native"}
+    default, native = {c.name: _wrw_plan(P, c, 15) for c, _ in rows}, {c.name: _wrw_plan(P, c, 0) for c, _ in rows}
+    fields = lambda p: [getattr(p, f) for f, _ in p._fields_]
+    for c, was in rows:
+        if was.startswith("tr<"):
+            want = _TR(2, 1) if was == "tr<3>/M64" else _TR(4, 0) if was == "tr<5,64x64>" else _TR(2, 1)
+            p = default[c.name]
+            assert ("WRW_TR", p.mt, p.w32, p.ng) == want, (c.name, was)
+    for knob, value, expect in KNOB_EXPECT:
+        P.set_knob(knob, value)
+        for c, was in rows:
+            p = _wrw_plan(P, c, 15)
+            if was in expect or (was == "tr<3>/M64" and "tr<3>" in expect):
+                family, mt, w32, ng = expect.get(was, expect["tr<3>"])
+                assert (p.family, p.mt, p.w32, p.ng) == (getattr(P, family), mt, w32, ng), (knob, value, c.name, was, p.family, p.mt, p.w32, p.ng)
+                assert p.block == (256 * ng if family == "WRW_TR" else 256), (knob, c.name)
+            else:                                          # 1-tap and native rows: these switches are about 5 and 3 taps
+                assert fields(p) == fields(default[c.name]), (knob, value, c.name)
+            assert fields(_wrw_plan(P, c, 0)) == fields(native[c.name]), (knob, value, c.name)       # fp32 arithmetic: no switch applies
+        P.set_knob(knob, P.knobs[knob])
+    # GLOWTTS_CONV32_1X1 = 0: plain 1x1 convolutions on 80- / 64-frame tiles — where the small-grid rule does not ask for 32 anyway
+    for value, nt in ((1, 32), (0, 80)):
+        P.set_knob("CONV32_1X1", value)
+        for mode in MODES:
+            assert _fwd_plan(P, KNOB_1X1, mode).frame_tile == nt, (value, mode)
+        for c in FWD:                                      # the tables' shapes are all below 380 workgroups: the switch changes nothing
+            mir = _fwd_mirror(c)
+            assert _fwd_plan(P, c, 0).frame_tile == (32 if mir.use32 else 80 if mir.n5 else 64), (value, c.name)
+
+
+def test_batch_plans_count_their_launches(P):
+    """glowtts_conv_wrw_batch: whether a group of up to four problems goes as ONE launch is plan_conv_wrw's answer (only the
+    bf16-plane kernels take a batch); the plan of an armed call describes the first launch and counts all of them."""
+    def batch(c, n, mode):
+        A = _Addr()
+        arr = lambda: (ctypes.c_void_p * n)(*[A() for _ in range(n)])
+        x, d, dwp, dbias = arr(), arr(), arr(), (arr() if c.dbias else None)
+        return _planned(P, mode, "glowtts_conv_wrw_batch", n, x, c.Cin * c.T, d, c.M * c.T, None, 0, 0, A() if c.mask else None,
+                        A() if c.mask_x else None, dwp, dbias, c.B, c.Cin, c.M, c.T, c.taps, c.dil, c.pad)
+
+    rows = {c.name: c for c in WRW}
+    for name, n, want15 in (("f5-M64", 6, (P.WRW_TR, 4, 2)),        # 5 taps, M % 64 == 0: groups of 4 and 2, one launch each
+                            ("f1-64", 5, (P.WRW_SPLIT, 4, 2)),       # the 1-tap bf16-plane kernel takes a batch as well: 4 + 1
+                            ("f5-mt4", 6, (P.WRW_FP, 0, 6)),         # M = 36: no plane kernel, so problem by problem in either mode
+                            ("g-T37", 3, (P.WRW_GENERIC, 0, 6))):    # generic kernel + row sums: two launches per problem
+        c = rows[name]
+        one = _wrw_plan(P, c, 0)
+        p0 = batch(c, n, 0)
+        assert (p0.family, p0.nbatch, p0.launches) == (one.family, 0, n * one.launches), (name, p0.family, p0.nbatch, p0.launches)
+        assert (p0.grid_x, p0.grid_y, p0.grid_z, p0.nb) == (one.grid_x, one.grid_y, one.grid_z, one.nb), name
+        p15 = batch(c, n, 15)
+        assert (p15.family, p15.nbatch, p15.launches) == want15, (name, p15.family, p15.nbatch, p15.launches)
+        if p15.nbatch:
+            single = _wrw_plan(P, c, 15)
+            assert p15.grid_x == single.grid_x and p15.grid_z % p15.nbatch == 0 and p15.lds_bytes == single.lds_bytes, name
+
+
+@gpu
+def test_an_armed_call_launches_nothing(G):
+    """glowtts_conv_plan_next on the GPU, at the first FWD and the first WRW row: the armed call returns 0, fills the plan and leaves
+    every guarded output buffer at GUARD; the same call again, unarmed, gives the row's result."""
+    c, plan = FWD[0], G.hip.ConvPlan()
+    I = _fwd_inputs(c.name, "random")
+    y = _fwd_launch(G, c, I, 0, arm=plan)
+    assert bool((y == GUARD).all()) and plan.family == G.hip.CONSTANTS["GLOWTTS_PLAN_GENERIC"] and plan.launches == 1
+    want, scale = _fwd_ref(c, I, F64)
+    _check_elem(f"conv_fwd {c.name} after an armed call", "y", "y", _fwd_launch(G, c, I, 0), want, scale, "random", 0, [])
+
+    c = WRW[0]
+    I = _wrw_inputs(c.name, "random")
+    want = _wrw_ref(c, I, F64)
+    for armed in (True, False):
+        D = _Dev()
+        dwp, dbias = D.out("dwp", c.taps * c.Cin * c.M, None if armed else 0.0), D.out("dbias", c.M, None if armed else 0.0)
+        args = [D.inp("x", I.x), c.Cin * c.T, D.inp("d", I.d), c.M * c.T, D.inp("mask", I.mask), D.inp("mask_x", I.mask), dwp, dbias,
+                c.B, c.Cin, c.M, c.T, c.taps, c.dil, c.pad]
+        _set_mode(G, 0)
+        if armed:
+            assert G.lib.glowtts_conv_plan_next(ctypes.byref(plan)) == 0
+        G.hip.call("glowtts_conv_wrw", *args)
+        if armed:
+            _untouched(D, "armed glowtts_conv_wrw")
+            assert plan.family == G.hip.CONSTANTS["GLOWTTS_PLAN_WRW_GENERIC"] and plan.launches == 2
+        r = D.finish()
+        if not armed:
+            for name, (value, terms) in want.items():
+                _check_red(f"conv_wrw {c.name} after an armed call", name, r[name].reshape(value.shape), value, terms, "random", [])
 
 
 def _fp32_cpu_figures():

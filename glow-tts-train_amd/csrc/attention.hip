@@ -15,9 +15,12 @@
 // relative-value term); phase 2 becomes the softmax backward dS = P (dP - sum_j P dP) * keep/scale; B2 = K, E2 = E_k
 // give dQ; dS is written to HBM for the second half (attn_dkv_kernel: dV = dO Pd, dK = Q dS, contraction over
 // queries) and for the two small embedding-gradient reductions (attn_relgrad_kernel).
-// Limits: d_k % 16 == 0, d_k <= 128, window <= 7.  T <= 256: strip in LDS; 256 < T <= 512: the LONG form below (strip in registers);
-// T > 512: attention_long.hip (plain tiled kernels through the (B, h, T, T) matrices; the backward's dK / dV kernel here has no limit).
+// Limits: d_k % 16 == 0, d_k <= 128, window <= 7; every T within them is served (attn_plan.hpp decides, tests/test_attention_kernels.py
+// sweeps it).  T <= 256 and d_k <= 96, or a shorter T beside a wider head: strip in LDS; else up to T = 512 the LONG form below (strip
+// in registers); T > 512: attention_long.hip (plain tiled kernels through the (B, h, T, T) matrices; the backward's dK / dV kernel
+// here has no limit).
 #include "common.hpp"
+#include "attn_plan.hpp"
 
 namespace glowtts {
 
@@ -57,8 +60,7 @@ __device__ __forceinline__ f32x4 mma_bf16(bf16x4_s a, bf16x4_s b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
 }
 
-constexpr int kAP = 80;    // LDS pitch of the [d][64 queries] A block          (== 16 mod 32)
-constexpr int kBP = 68;    // LDS pitch of the [d][64 keys] B tile              (==  4 mod 32)
+// kAP = 80, kBP = 68, kCP = 68: the LDS pitches of the A block, the B tile and a wave's probability chunk (attn_plan.hpp)
 
 __device__ __forceinline__ float group16_max(float v) {
 #pragma unroll
@@ -155,7 +157,8 @@ __device__ unsigned long long g_attn_trace[1024 * 8];
 // them through a per-wave [16 queries][64 keys] LDS chunk, one key tile at a time (same wave writes and reads: no barrier); the
 // band P[i][i + r - w] the relative-value term needs is collected in a per-wave [16][16] table while phase 2 passes the
 // diagonal tiles; the backward (MODE 1) reads its probabilities from HBM into registers instead of an LDS strip.
-constexpr int kCP = 68;    // LDS pitch of a wave's [16][64] probability chunk (LONG)
+// The same form serves T <= 256 where the LDS strip does not fit beside a wide head (d_k = 112 from T = 225, d_k = 128 from T = 193:
+// plan_attn): every loop over the strip is guarded by t < ntile / jt < njt, so fewer than 17 tiles are as good as more.
 
 template <int MODE, bool BF, int NT, int DTC, bool LONG = false>
 __global__ __launch_bounds__(256) void attn_qblock_kernel(AttnParams p) {
@@ -750,8 +753,8 @@ __global__ __launch_bounds__(256) void attn_dkv_kernel(AttnDkvParams p) {
 // embedding gradients: dE[r][d] += sum_i M[i][i + r - w] * A[d][i]   (M, A) = (Pd, dO) -> dE_v ; (dS, Q) -> dE_k
 // workgroup = one (utterance, head, slab of DC channels): the 2w+1 diagonals of Pd / dS and the slab's dO / Q rows are
 // staged in LDS once (coalesced, 8 loads in flight per thread); then thread = one (r, d) output walks the queries out
-// of LDS.  DC is chosen by the host so that (2w+1) * DC <= 256 outputs — one per thread — and the slab fits LDS at
-// T = 256 whatever the head width.
+// of LDS.  DC is chosen by the host (attn_relgrad_dc) so that (2w+1) * DC <= 256 outputs — one per thread — and the slab
+// fits LDS at every T <= 512: 8 <= DC <= d_k, the last slab of a head may be partial (nd).
 __global__ __launch_bounds__(256) void attn_relgrad_kernel(const float *__restrict__ p, const float *__restrict__ ds,
                                                            const unsigned char *__restrict__ drop, float drop_scale,
                                                            const float *__restrict__ dout, const float *__restrict__ q,
@@ -823,7 +826,6 @@ int attn_long_backward(const float *dout, const float *q, const float *k, const 
                        const float *mask, const unsigned char *drop, float drop_scale, const float *p_attn, float *ds, float *dq,
                        float *demb_k, float *demb_v, int B, int H, int T, int dk, int w, int e_hs, int block_len, float scale,
                        bool relgrad, hipStream_t s);
-constexpr int kAttnStripMaxT = 512;
 
 static int attn_check(const char *name, int B, int H, int T, int dk, int w) {
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0 && dk > 0, "%s: bad shape", name);
@@ -832,17 +834,11 @@ static int attn_check(const char *name, int B, int H, int T, int dk, int w) {
     return 0;
 }
 
-static size_t attn_lds(int dk, int TP, bool lng) {
-    const size_t strip = lng ? (size_t)4 * 16 * kCP + 4 * 16 * 16 : (size_t)64 * TP;
-    return ((size_t)dk * kAP + (size_t)dk * kBP + strip + (size_t)16 * (dk + 4) + (size_t)16 * (dk + 16) + 4 * 16 * 17) *
-               sizeof(float) + (size_t)64 * TP;        // + the keep bytes of the strip
-}
-
 template <int MODE, bool BF, int NT, int DTC, bool LONG = false>
-static int attn_launch_nt(AttnParams &p, hipStream_t s) {
-    p.TP = ((p.T + 15) / 16) * 16 + 4;
-    const size_t lds = attn_lds(p.dk, p.TP, LONG);
-    GLOWTTS_CHECK_ARG(lds <= 160 * 1024, "glowtts_rel_attn: needs %zu B of LDS", lds);
+static int attn_launch_nt(AttnParams &p, const AttnPlan &plan, hipStream_t s) {
+    p.TP = attn_tp(p.T);
+    const size_t lds = (size_t)plan.lds_qblock;
+    GLOWTTS_CHECK_ARG(lds <= kAttnLdsMax && p.T <= 16 * NT, "glowtts_rel_attn: needs %zu B of LDS", lds);
     static LdsLimit attr_max_e;   // per device: raised only when a launch needs more than any earlier one
     if (int rc_ = attr_max_e.ensure(reinterpret_cast<const void *>(&attn_qblock_kernel<MODE, BF, NT, DTC, LONG>), lds, "glowtts_rel_attn")) return rc_;
     dim3 grid((p.T + 63) / 64, p.H, p.B);
@@ -850,17 +846,27 @@ static int attn_launch_nt(AttnParams &p, hipStream_t s) {
     GLOWTTS_LAUNCH_CHECK("glowtts_rel_attn");
 }
 
+// the one ladder from a plan's form and head-width flag to an instantiation of the q-block kernel
 template <int MODE, bool BF>
-static int attn_launch(AttnParams &p, hipStream_t s) {
-    if (p.T > 256)           // the strip in registers only (round 4): 256 < T <= 512
-        return p.dk == 96 ? attn_launch_nt<MODE, BF, 32, 6, true>(p, s) : attn_launch_nt<MODE, BF, 32, 0, true>(p, s);
-    if (p.dk == 96) return p.T <= 160 ? attn_launch_nt<MODE, BF, 10, 6>(p, s) : attn_launch_nt<MODE, BF, 16, 6>(p, s);
-    return p.T <= 160 ? attn_launch_nt<MODE, BF, 10, 0>(p, s) : attn_launch_nt<MODE, BF, 16, 0>(p, s);
+static int attn_launch(AttnParams &p, const AttnPlan &plan, hipStream_t s) {
+    switch (plan.form) {
+    case GLOWTTS_ATTN_SHORT10: return plan.dk96 ? attn_launch_nt<MODE, BF, 10, 6>(p, plan, s) : attn_launch_nt<MODE, BF, 10, 0>(p, plan, s);
+    case GLOWTTS_ATTN_SHORT16: return plan.dk96 ? attn_launch_nt<MODE, BF, 16, 6>(p, plan, s) : attn_launch_nt<MODE, BF, 16, 0>(p, plan, s);
+    case GLOWTTS_ATTN_STRIP32: return plan.dk96 ? attn_launch_nt<MODE, BF, 32, 6, true>(p, plan, s) : attn_launch_nt<MODE, BF, 32, 0, true>(p, plan, s);
+    }
+    GLOWTTS_CHECK_ARG(false, "glowtts_rel_attn: no q-block kernel for form %d", (int)plan.form);
 }
 
 }  // namespace glowtts
 
 using namespace glowtts;
+
+extern "C" int glowtts_attn_plan_for(int T, int dk, int window, int bf16_mma, int backward, glowtts_attn_plan *out) {
+    GLOWTTS_CHECK_ARG(out != nullptr, "glowtts_attn_plan_for: null pointer");
+    if (int rc = attn_check("glowtts_attn_plan_for", 1, 1, T, dk, window)) return rc;
+    *out = T == 0 ? AttnPlan{} : plan_attn(T, dk, window < 0 ? -1 : window, bf16_mma != 0, backward != 0);
+    return 0;
+}
 
 extern "C" int glowtts_rel_attn_fwd_ex(const float *q, const float *k, const float *v, const float *emb_k, const float *emb_v,
                                        const float *mask, const unsigned char *drop, float drop_scale, float *p_attn,
@@ -874,10 +880,11 @@ extern "C" int glowtts_rel_attn_fwd_ex(const float *q, const float *k, const flo
     p.B = B; p.H = H; p.T = T; p.dk = dk; p.w = emb_k ? window : -1; p.block_len = block_len;
     p.e_hs = heads_share ? 0 : (2 * window + 1) * dk;
     p.scale = 1.0f / sqrtf((float)dk); p.drop_scale = drop_scale;
-    if (T > kAttnStripMaxT)
+    const AttnPlan plan = plan_attn(T, dk, p.w, bf16_mma != 0, false);
+    if (plan.form == GLOWTTS_ATTN_TILED)
         return attn_long_forward(q, k, v, emb_k, emb_v, mask, drop, drop_scale, p_attn, out, B, H, T, dk, window, p.e_hs, block_len,
                                  p.scale, (hipStream_t)stream);
-    return bf16_mma ? attn_launch<0, true>(p, (hipStream_t)stream) : attn_launch<0, false>(p, (hipStream_t)stream);
+    return plan.bf16 ? attn_launch<0, true>(p, plan, (hipStream_t)stream) : attn_launch<0, false>(p, plan, (hipStream_t)stream);
 }
 
 extern "C" int glowtts_rel_attn_fwd(const float *q, const float *k, const float *v, const float *emb_k, const float *emb_v,
@@ -904,38 +911,38 @@ extern "C" int glowtts_rel_attn_bwd_ex(const float *dout, const float *q, const 
     p.B = B; p.H = H; p.T = T; p.dk = dk; p.w = emb_k ? window : -1; p.block_len = block_len;
     p.e_hs = heads_share ? 0 : (2 * window + 1) * dk;
     p.scale = 1.0f / sqrtf((float)dk); p.drop_scale = drop_scale;
-    const bool long_form = T > kAttnStripMaxT;
+    const AttnPlan plan = plan_attn(T, dk, p.w, bf16_mma != 0, true);
+    const bool long_form = plan.form == GLOWTTS_ATTN_TILED;
     if (long_form) {
         if (int rc = attn_long_backward(dout, q, k, v, emb_k, emb_v, mask, drop, drop_scale, p_attn, ds, dq, demb_k, demb_v, B, H, T, dk,
                                         window, p.e_hs, block_len, p.scale, true, s))
             return rc;
-    } else if (int rc = bf16_mma ? attn_launch<1, true>(p, s) : attn_launch<1, false>(p, s)) return rc;
+    } else if (int rc = plan.bf16 ? attn_launch<1, true>(p, plan, s) : attn_launch<1, false>(p, plan, s)) return rc;
     AttnDkvParams d{};
     d.dout = dout; d.q = q; d.p = p_attn; d.ds = ds; d.drop = drop; d.dv = dv; d.dkk = dk_out;
     d.B = B; d.H = H; d.T = T; d.dk = dk; d.drop_scale = drop_scale;
-    const size_t lds = ((size_t)2 * dk * kBP + (size_t)2 * 64 * kAP) * sizeof(float);
+    const size_t lds = (size_t)plan.lds_dkv;
+    const bool bf = plan.bf16 != 0;   // the tiled form is fp32 throughout: the header promises that bf16_mma has no effect there
     {
-        const void *fn = bf16_mma ? (dk == 96 ? reinterpret_cast<const void *>(&attn_dkv_kernel<true, 6>) : reinterpret_cast<const void *>(&attn_dkv_kernel<true, 0>))
-                                  : (dk == 96 ? reinterpret_cast<const void *>(&attn_dkv_kernel<false, 6>) : reinterpret_cast<const void *>(&attn_dkv_kernel<false, 0>));
+        const void *fn = bf ? (plan.dk96 ? reinterpret_cast<const void *>(&attn_dkv_kernel<true, 6>) : reinterpret_cast<const void *>(&attn_dkv_kernel<true, 0>))
+                                  : (plan.dk96 ? reinterpret_cast<const void *>(&attn_dkv_kernel<false, 6>) : reinterpret_cast<const void *>(&attn_dkv_kernel<false, 0>));
         static LdsLimit lim[4];   // per device and instantiation: raised only when a launch needs more than any earlier one
-        if (int rc_ = lim[(bf16_mma ? 2 : 0) + (dk == 96 ? 1 : 0)].ensure(fn, lds, "glowtts_rel_attn_bwd")) return rc_;
+        if (int rc_ = lim[(bf ? 2 : 0) + (plan.dk96 ? 1 : 0)].ensure(fn, lds, "glowtts_rel_attn_bwd")) return rc_;
         const dim3 grid((T + 63) / 64, H, B);
-        if (bf16_mma) {
-            if (dk == 96) hipLaunchKernelGGL((attn_dkv_kernel<true, 6>), grid, dim3(256), lds, s, d);
+        if (bf) {
+            if (plan.dk96) hipLaunchKernelGGL((attn_dkv_kernel<true, 6>), grid, dim3(256), lds, s, d);
             else hipLaunchKernelGGL((attn_dkv_kernel<true, 0>), grid, dim3(256), lds, s, d);
         } else {
-            if (dk == 96) hipLaunchKernelGGL((attn_dkv_kernel<false, 6>), grid, dim3(256), lds, s, d);
+            if (plan.dk96) hipLaunchKernelGGL((attn_dkv_kernel<false, 6>), grid, dim3(256), lds, s, d);
             else hipLaunchKernelGGL((attn_dkv_kernel<false, 0>), grid, dim3(256), lds, s, d);
         }
     }
     if (emb_k && !long_form) {
-        const int nr = 2 * window + 1;
-        int DC = (256 / nr) & ~7;                      // one (r, d) output per thread, slab rows a multiple of 8
-        if (DC > dk) DC = dk;
-        const size_t lds_r = ((size_t)2 * nr * T + (size_t)2 * DC * (T + 1)) * sizeof(float);
+        const int DC = plan.relgrad_dc;                // one (r, d) output per thread, slab rows a multiple of 8, the slab within LDS
+        const size_t lds_r = (size_t)plan.lds_relgrad;
         static LdsLimit attr_max_r;   // per device: raised only when a launch needs more than any earlier one
-    if (int rc_ = attr_max_r.ensure(reinterpret_cast<const void *>(&attn_relgrad_kernel), lds_r, "glowtts_rel_attn_bwd")) return rc_;
-        hipLaunchKernelGGL(attn_relgrad_kernel, dim3(B * H, (dk + DC - 1) / DC), dim3(256), lds_r, s, p_attn, ds, drop,
+        if (int rc_ = attr_max_r.ensure(reinterpret_cast<const void *>(&attn_relgrad_kernel), lds_r, "glowtts_rel_attn_bwd")) return rc_;
+        hipLaunchKernelGGL(attn_relgrad_kernel, dim3(B * H, plan.relgrad_grid_y), dim3(256), lds_r, s, p_attn, ds, drop,
                            drop_scale, dout, q, demb_k, demb_v, H, T, dk, window, p.e_hs, DC);
     }
     GLOWTTS_LAUNCH_CHECK("glowtts_rel_attn_bwd");

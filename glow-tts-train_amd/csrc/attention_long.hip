@@ -11,6 +11,7 @@
 // Same definitions as attention.hip: keep(i, j) = mask_i mask_j != 0 and |j - i| <= block_len ; masked scores are -1e4 ; the
 // stored p is the softmax BEFORE dropout ; Pd = p * keep_byte * drop_scale.
 #include "common.hpp"
+#include "attn_plan.hpp"
 
 namespace glowtts {
 
@@ -242,7 +243,7 @@ int attn_long_backward(const float *dout, const float *q, const float *k, const 
     const int nt = (T + 63) / 64;
     const long rows = (long)B * H * T;
     if (emb_k && relgrad)        // dE_v from Pd and dO: before ds is needed (p_attn and the keep bytes are inputs)
-        hipLaunchKernelGGL(attn_long_relgrad_kernel, dim3(B * H, 2 * w + 1), dim3(256), (size_t)T * sizeof(float), s, p_attn, drop,
+        hipLaunchKernelGGL(attn_long_relgrad_kernel, dim3(B * H, 2 * w + 1), dim3(256), attn_lds_diag(T), s, p_attn, drop,
                            drop_scale, dout, demb_v, H, T, dk, w, e_hs);
     hipLaunchKernelGGL(attn_long_scores_kernel, dim3(nt, nt, B * H), dim3(256), 0, s, p);
     hipLaunchKernelGGL(attn_long_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ds, p_attn, mask, H, T, block_len, scale,
@@ -250,7 +251,7 @@ int attn_long_backward(const float *dout, const float *q, const float *k, const 
     hipLaunchKernelGGL(attn_long_apply_kernel, dim3(nt, (dk + 63) / 64, B * H), dim3(256), 0, s, ds, nullptr, 1.f, k,
                        emb_k ? emb_k : nullptr, dq, H, T, dk, emb_k ? w : -1, e_hs);
     if (emb_k && relgrad)        // dE_k from dS and Q
-        hipLaunchKernelGGL(attn_long_relgrad_kernel, dim3(B * H, 2 * w + 1), dim3(256), (size_t)T * sizeof(float), s, ds, nullptr, 1.f, q,
+        hipLaunchKernelGGL(attn_long_relgrad_kernel, dim3(B * H, 2 * w + 1), dim3(256), attn_lds_diag(T), s, ds, nullptr, 1.f, q,
                            demb_k, H, T, dk, w, e_hs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { set_error("glowtts_rel_attn_bwd (long form): launch failed: %s", hipGetErrorString(e)); return (int)e; }

@@ -735,9 +735,11 @@ int glowtts_flow_block_bwd_io(const glowtts_flow_block *blk, const void *x, cons
  * drop_scale, or NULL.  p_attn (B, H, T, T) receives softmax(P) BEFORE dropout (saved for the backward).
  * fwd : scores = (q_i.k_j + q_i.emb_k[j-i+w]) / sqrt(dk) ; out_i = sum_j Pd_ij v_j + sum_r Pd[i][i+r-w] emb_v[r]
  * bwd : dq, dk, dv (B, H*dk, T) written; demb_k / demb_v accumulated; ds (B, H, T, T) is scratch (scaled score grads).
- * Limits: dk % 16 == 0, dk <= 128, window <= 7; any T: MFMA kernels with the 64-query score strip on the chip up to 512 tokens
- * (in LDS to 256, in registers to 512), plain tiled kernels through p_attn / ds beyond (csrc/attention_long.hip; the bf16_mma
- * switch of the _ex forms has no effect there).
+ * Limits: dk % 16 == 0, dk <= 128, window <= 7; any T, and every shape within these limits is served: MFMA kernels with the
+ * 64-query score strip on the chip up to 512 tokens (the probabilities in LDS up to T = 256 where they fit beside the head: every
+ * dk <= 96, dk = 112 to T = 224, dk = 128 to T = 192; in registers otherwise), plain tiled kernels through p_attn / ds beyond
+ * (csrc/attention_long.hip; the bf16_mma switch of the _ex forms has no effect there).  The embedding-gradient reduction takes
+ * slabs of 8 .. dk channels so that it fits LDS at every T <= 512.  glowtts_attn_plan_for below says what a call launches.
  * The `_ex` forms take bf16_mma: 0 = exactly the functions above (v_mfma_f32_16x16x4_f32); 1 = the contractions
  * (q k^T, q emb_k^T, P v, P_w emb_v, and dP, dq, dk, dv in the backward) on v_mfma_f32_16x16x16_bf16 with fp32
  * accumulation — operands are rounded to bf16 (nearest even) in registers as they leave LDS; q, k, v, p_attn, the
@@ -760,6 +762,31 @@ int glowtts_rel_attn_bwd_ex(const float *dout, const float *q, const float *k, c
                             const float *p_attn, float *ds, float *dq, float *dk_out, float *dv, float *demb_k,
                             float *demb_v, int B, int H, int T, int dk, int window, int heads_share, int block_len,
                             int bf16_mma, glowtts_stream_t stream);
+
+/* ---- what would this attention call launch?  (no reference counterpart; csrc/attn_plan.hpp) ---------------------------------
+ * The decision glowtts_rel_attn_fwd_ex (backward = 0) / _bwd_ex (backward = 1) make for T tokens, head width dk and `window`
+ * (negative: no relative embeddings, as with emb_k = NULL) — a pure host function: it touches no device and works on a machine
+ * without a GPU.  Non-zero (and glowtts_last_error) for the argument errors of those calls (dk, window).  T = 0: all zero.
+ *   form           : GLOWTTS_ATTN_* below
+ *   dk96           : 1 = the instantiations with the head width 96 compiled in (q-block and dK / dV kernels)
+ *   bf16           : the arithmetic in force: bf16_mma, but 0 in the tiled form
+ *   lds_qblock     : dynamic LDS bytes of the q-block kernel (0 in the tiled form, whose kernels use static LDS)
+ *   lds_dkv        : ... of the dK / dV kernel (backward)
+ *   lds_relgrad    : ... of each embedding-gradient launch (backward with a window)
+ *   relgrad_dc     : channels per slab of that reduction (0 in the tiled form: one workgroup per offset, no slab)
+ *   relgrad_grid_y : its grid's y: slabs per head (tiled form: the 2 window + 1 offsets)
+ *   launches       : kernel launches of the call */
+#define GLOWTTS_ATTN_SHORT10 1 /* T <= 160: score strip in 10 accumulator tiles, probabilities in LDS */
+#define GLOWTTS_ATTN_SHORT16 2 /* T <= 256: 16 tiles, probabilities in LDS */
+#define GLOWTTS_ATTN_STRIP32 3 /* T <= 512: 32 tiles, probabilities stay in registers */
+#define GLOWTTS_ATTN_TILED 4   /* plain tiled kernels through p_attn / ds */
+typedef struct glowtts_attn_plan {
+    int32_t form, dk96, bf16;
+    int32_t lds_qblock, lds_dkv, lds_relgrad;
+    int32_t relgrad_dc, relgrad_grid_y;
+    int32_t launches;
+} glowtts_attn_plan;
+int glowtts_attn_plan_for(int T, int dk, int window, int bf16_mma, int backward, glowtts_attn_plan *out);
 
 /* ---- channel LayerNorm with fused residual (csrc/norm.hip) -----------------------------------------------------
  * replaces LayerNorm.forward (layers.py:19-28) and the `x + y` before it (attentions.py:68,72):

@@ -134,13 +134,15 @@ template <> struct VecIO<1, true> {
 
 static inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// 16-byte path is legal when every row start is 16-B aligned: T % 4 == 0 and all bases aligned.
-static inline bool can_vec4(int T, std::initializer_list<const void *> ptrs) {
-    if (T & 3) return false;
+// every base 16-B aligned (a null one counts as aligned)
+static inline bool all_aligned16(std::initializer_list<const void *> ptrs) {
     for (const void *p : ptrs)
         if (p && !aligned16(p)) return false;
     return true;
 }
+
+// 16-byte path is legal when every row start is 16-B aligned: T % 4 == 0 and all bases aligned.
+static inline bool can_vec4(int T, std::initializer_list<const void *> ptrs) { return (T & 3) == 0 && all_aligned16(ptrs); }
 
 // The same decision for a FLAT buffer of n floats, taken once per launch: `launch(width, count)` is called with
 // std::integral_constant<int, 4> and n / 4 when n % 4 == 0 and every pointer is 16-B aligned (a null one counts as aligned), else
@@ -151,6 +153,20 @@ static inline void vec4_or_scalar(long n, std::initializer_list<const void *> pt
     for (const void *p : ptrs) wide = wide && aligned16(p);
     if (wide) launch(std::integral_constant<int, 4>{}, n / 4);
     else launch(std::integral_constant<int, 1>{}, n);
+}
+
+// Run-time values as compile-time ones, for the same kind of launch line: `f` is called with std::true_type / std::false_type for a
+// bool, and with std::integral_constant<int, N> for an int that is one of the listed Ns (false, and no call, when it is none of
+// them).  Only the listed values are instantiated; nesting two of them instantiates their product, so a kernel whose forms are
+// no full product is given ONE int that enumerates the forms it has.
+template <class F>
+static inline void as_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int... Ns, class F>
+static inline bool as_one_of(int v, F &&f) {
+    return ((v == Ns ? (f(std::integral_constant<int, Ns>{}), true) : false) || ...);
 }
 
 // Dynamic-LDS limit of one kernel (`static LdsLimit x;` at the launch site): hipFuncSetAttribute is per DEVICE, so the

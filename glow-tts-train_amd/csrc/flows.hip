@@ -10,6 +10,7 @@
 // Per-channel / per-matrix reductions are wave-shuffle + LDS partial sums followed by ONE float atomic per
 // workgroup and output element (global_atomic_add_f32, executed at the memory side: MI355X_MICROARCH.md).
 #include "common.hpp"
+#include "flow_plan.hpp"
 
 namespace glowtts {
 
@@ -520,6 +521,53 @@ __device__ __forceinline__ float row_sum_256(const float *part, int pitch, int r
     return s;
 }
 
+// The tail of the two fused backward kernels (actnorm_invconv_bwd_kernel, coupling_ai_bwd_kernel): al / ab = a thread's partial
+// sums of dlogs / dbias for the N channels of group g, aw = of the N x N entries of dW.
+template <int N>
+__device__ __forceinline__ void flow_param_sums(const float (&al)[N], const float (&ab)[N], const float (&aw)[N * N],
+                                                const float *__restrict__ dlogdet, const float *__restrict__ x_len,
+                                                const float *__restrict__ w_inv, float *__restrict__ dlogs,
+                                                float *__restrict__ dbias, float *__restrict__ dw, int g, int B, int C) {
+    // one LDS round for all 2N + N*N sums, then ONE atomic instruction per output cache line: same-line float atomics
+    // retire serially in L2, so a workgroup must not send them one by one
+    constexpr int NS = 2 * N + N * N;
+    constexpr int RP = 260;                         // row pitch (floats): 16-byte aligned rows, 4 banks apart
+    __shared__ __attribute__((aligned(16))) float part[NS * RP + 4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) { part[k * RP + tid] = al[k]; part[(N + k) * RP + tid] = ab[k]; }
+#pragma unroll
+    for (int q = 0; q < N * N; ++q) part[(2 * N + q) * RP + tid] = aw[q];
+    if (wave == 3) {                                // sum_b dlogdet[b] * x_len[b]: feeds dlogs (every channel) and dW
+        float t = 0.f;
+        if (dlogdet != nullptr)
+            for (int b = lane; b < B; b += 64) t += dlogdet[b] * x_len[b];
+        t = wave_sum(t);
+        if (lane == 0) part[NS * RP] = t;
+    }
+    __syncthreads();
+    const float tt = part[NS * RP];
+    if (wave == 0) {                                // rows [0, 2N): dlogs, dbias
+        int q; bool owner;
+        float v = row_sum_256<2 * N>(part, RP, 0, lane, q, owner);
+        if (owner) {
+            if (q < N) {
+                if (blockIdx.y == 0) v += tt;
+                atomicAdd(dlogs + invconv_channel<N>(q, g, C), v);
+            } else {
+                atomicAdd(dbias + invconv_channel<N>(q - N, g, C), v);
+            }
+        }
+    } else if (wave == 1) {                         // rows [2N, 2N + N*N): dW, one instruction for the whole matrix
+        int r; bool owner;
+        float v = row_sum_256<N * N>(part, RP, 2 * N, lane, r, owner);
+        if (owner) {
+            if (g == 0 && blockIdx.y == 0 && dlogdet != nullptr) v += w_inv[(r % N) * N + r / N] * (float)(C / N) * tt;
+            atomicAdd(dw + r, v);
+        }
+    }
+}
+
 template <int N, int V, bool B16 = false>
 __global__ __launch_bounds__(256) void actnorm_invconv_bwd_kernel(const void *__restrict__ x, const float *__restrict__ mask,
                                                                   const float *__restrict__ logs, const float *__restrict__ bias,
@@ -600,44 +648,7 @@ __global__ __launch_bounds__(256) void actnorm_invconv_bwd_kernel(const void *__
         it = nx;
         have = have_nx;
     }
-    // one LDS round for all 2N + N*N sums, then ONE atomic instruction per output cache line: same-line float atomics
-    // retire serially in L2, so a workgroup must not send them one by one
-    constexpr int NS = 2 * N + N * N;
-    constexpr int RP = 260;                         // row pitch (floats): 16-byte aligned rows, 4 banks apart
-    __shared__ __attribute__((aligned(16))) float part[NS * RP + 4];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < N; ++k) { part[k * RP + tid] = al[k]; part[(N + k) * RP + tid] = ab[k]; }
-#pragma unroll
-    for (int q = 0; q < N * N; ++q) part[(2 * N + q) * RP + tid] = aw[q];
-    if (wave == 3) {                                // sum_b dlogdet[b] * x_len[b]: feeds dlogs (every channel) and dW
-        float t = 0.f;
-        if (dlogdet != nullptr)
-            for (int b = lane; b < B; b += 64) t += dlogdet[b] * x_len[b];
-        t = wave_sum(t);
-        if (lane == 0) part[NS * RP] = t;
-    }
-    __syncthreads();
-    const float tt = part[NS * RP];
-    if (wave == 0) {                                // rows [0, 2N): dlogs, dbias
-        int q; bool owner;
-        float v = row_sum_256<2 * N>(part, RP, 0, lane, q, owner);
-        if (owner) {
-            if (q < N) {
-                if (blockIdx.y == 0) v += tt;
-                atomicAdd(dlogs + invconv_channel<N>(q, g, C), v);
-            } else {
-                atomicAdd(dbias + invconv_channel<N>(q - N, g, C), v);
-            }
-        }
-    } else if (wave == 1) {                         // rows [2N, 2N + N*N): dW, one instruction for the whole matrix
-        int r; bool owner;
-        float v = row_sum_256<N * N>(part, RP, 2 * N, lane, r, owner);
-        if (owner) {
-            if (g == 0 && blockIdx.y == 0 && dlogdet != nullptr) v += w_inv[(r % N) * N + r / N] * (float)(C / N) * tt;
-            atomicAdd(dw + r, v);
-        }
-    }
+    flow_param_sums<N>(al, ab, aw, dlogdet, x_len, w_inv, dlogs, dbias, dw, g, B, C);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -898,50 +909,39 @@ __global__ __launch_bounds__(256) void coupling_ai_bwd_kernel(const float *__res
             }
         }
     }
-    constexpr int NS = 2 * N + N * N;
-    constexpr int RP = 260;
-    __shared__ __attribute__((aligned(16))) float part[NS * RP + 4];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < N; ++k) { part[k * RP + tid] = al[k]; part[(N + k) * RP + tid] = ab[k]; }
-#pragma unroll
-    for (int q = 0; q < N * N; ++q) part[(2 * N + q) * RP + tid] = aw[q];
-    if (wave == 3) {
-        float t = 0.f;
-        if (dlogdet != nullptr)
-            for (int b = lane; b < B; b += 64) t += dlogdet[b] * x_len[b];
-        t = wave_sum(t);
-        if (lane == 0) part[NS * RP] = t;
-    }
-    __syncthreads();
-    const float tt = part[NS * RP];
-    if (wave == 0) {
-        int q; bool owner;
-        float v = row_sum_256<2 * N>(part, RP, 0, lane, q, owner);
-        if (owner) {
-            if (q < N) {
-                if (blockIdx.y == 0) v += tt;
-                atomicAdd(dlogs + invconv_channel<N>(q, g, C), v);
-            } else {
-                atomicAdd(dbias + invconv_channel<N>(q - N, g, C), v);
-            }
-        }
-    } else if (wave == 1) {
-        int r; bool owner;
-        float v = row_sum_256<N * N>(part, RP, 2 * N, lane, r, owner);
-        if (owner) {
-            if (g == 0 && blockIdx.y == 0 && dlogdet != nullptr) v += w_inv[(r % N) * N + r / N] * (float)(C / N) * tt;
-            atomicAdd(dw + r, v);
-        }
-    }
+    flow_param_sums<N>(al, ab, aw, dlogdet, x_len, w_inv, dlogs, dbias, dw, g, B, C);
 }
 
 }  // namespace glowtts
 
 // ================================================================================================================
-// C ABI
+// C ABI: check the arguments, plan (flow_plan.hpp), one launch line
 // ================================================================================================================
 using namespace glowtts;
+
+// The shape checks of the entry point behind `op`, shared with glowtts_flow_plan_for
+static int flow_check(int op, const char *name, int B, int C, int T, int n_split) {
+    const bool invconv = op == GLOWTTS_FLOW_INVCONV_FWD || op == GLOWTTS_FLOW_INVCONV_BWD;
+    const bool fused = op == GLOWTTS_FLOW_ACTNORM_INVCONV_FWD || op == GLOWTTS_FLOW_ACTNORM_INVCONV_BWD ||
+                       op == GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_FWD || op == GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_BWD;
+    const bool halves = op >= GLOWTTS_FLOW_COUPLING_FWD;        // the coupling's two halves: C even
+    GLOWTTS_CHECK_ARG(op >= GLOWTTS_FLOW_ACTNORM_FWD && op <= GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_BWD, "%s: no operation %d", name, op);
+    if (invconv)
+        GLOWTTS_CHECK_ARG(n_split >= 2 && n_split % 2 == 0 && n_split <= kInvConvMaxN,
+                          "%s: n_split=%d (supported: even values up to %d)", name, n_split, kInvConvMaxN);
+    if (fused) GLOWTTS_CHECK_ARG(n_split == 2 || n_split == 4, "%s: n_split=%d (fused path: 2 or 4)", name, n_split);
+    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0, "%s: bad shape (%d,%d,%d)", name, B, C, T);
+    if (invconv || fused) GLOWTTS_CHECK_ARG(C % n_split == 0, "%s: bad shape: C=%d not divisible by n_split=%d", name, C, n_split);
+    if (halves) GLOWTTS_CHECK_ARG(C % 2 == 0, "%s: bad shape: C=%d is odd", name, C);
+    return 0;
+}
+
+extern "C" int glowtts_flow_plan_for(int op, int B, int C, int T, int n_split, int reverse, int aligned, glowtts_flow_plan *out) {
+    GLOWTTS_CHECK_ARG(out != nullptr, "glowtts_flow_plan_for: null pointer");
+    if (int rc = flow_check(op, "glowtts_flow_plan_for", B, C, T, n_split)) return rc;
+    *out = (long)B * C * T == 0 ? FlowPlan{} : plan_flow(op, B, C, T, n_split, reverse != 0, aligned != 0);
+    return 0;
+}
 
 extern "C" int glowtts_mask_len(const float *mask, float *x_len, int B, int T, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(mask && x_len && B >= 0 && T >= 0, "glowtts_mask_len: bad argument");
@@ -954,59 +954,42 @@ extern "C" int glowtts_actnorm_fwd(const float *x, const float *mask, const floa
                                    const float *x_len, float *z, float *logdet, int B, int C, int T, int reverse,
                                    glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && logs && bias && z, "glowtts_actnorm_fwd: null pointer");
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0, "glowtts_actnorm_fwd: bad shape (%d,%d,%d)", B, C, T);
+    if (int rc = flow_check(GLOWTTS_FLOW_ACTNORM_FWD, "glowtts_actnorm_fwd", B, C, T, 0)) return rc;
     GLOWTTS_CHECK_ARG(reverse || !logdet || x_len, "glowtts_actnorm_fwd: logdet requested without x_len");
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, mask, z});
-    const long n = (long)B * C * (v4 ? T / 4 : T);
-    const int grid = cdiv(n, 256);
-    if (reverse) {
-        if (v4) hipLaunchKernelGGL((actnorm_fwd_kernel<4, true>), dim3(grid), dim3(256), 0, s, x, mask, logs, bias, x_len, z, logdet, B, C, T);
-        else    hipLaunchKernelGGL((actnorm_fwd_kernel<1, true>), dim3(grid), dim3(256), 0, s, x, mask, logs, bias, x_len, z, logdet, B, C, T);
-    } else {
-        if (v4) hipLaunchKernelGGL((actnorm_fwd_kernel<4, false>), dim3(grid), dim3(256), 0, s, x, mask, logs, bias, x_len, z, logdet, B, C, T);
-        else    hipLaunchKernelGGL((actnorm_fwd_kernel<1, false>), dim3(grid), dim3(256), 0, s, x, mask, logs, bias, x_len, z, logdet, B, C, T);
-    }
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_ACTNORM_FWD, B, C, T, 0, reverse != 0, all_aligned16({x, mask, z}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_bool(reverse != 0, [&](auto REV) {
+        hipLaunchKernelGGL((actnorm_fwd_kernel<V, REV>), dim3(pl.grid_x), dim3(256), 0, (hipStream_t)stream, x, mask, logs, bias, x_len,
+                           z, logdet, B, C, T);
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_actnorm_fwd");
-}
-
-static inline int slab_size(int B, int C) {
-    // enough workgroups to fill 256 CUs several times over, at least one utterance per workgroup
-    int nbk = (2048 + C - 1) / C;
-    if (nbk > B) nbk = B;
-    if (nbk < 1) nbk = 1;
-    return (B + nbk - 1) / nbk;
 }
 
 extern "C" int glowtts_actnorm_bwd(const float *x, const float *mask, const float *logs, const float *dz,
                                    const float *dlogdet, const float *x_len, float *dx, float *dlogs, float *dbias,
                                    int B, int C, int T, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && logs && dz && dx && dlogs && dbias, "glowtts_actnorm_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0, "glowtts_actnorm_bwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_ACTNORM_BWD, "glowtts_actnorm_bwd", B, C, T, 0)) return rc;
     GLOWTTS_CHECK_ARG(!dlogdet || x_len, "glowtts_actnorm_bwd: dlogdet given without x_len");
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const int nb = slab_size(B, C);
-    dim3 grid(C, (B + nb - 1) / nb);
-    if (can_vec4(T, {x, mask, dz, dx}))
-        hipLaunchKernelGGL((actnorm_bwd_kernel<4>), grid, dim3(256), 0, s, x, mask, logs, dz, dlogdet, x_len, dx, dlogs, dbias, B, C, T, nb);
-    else
-        hipLaunchKernelGGL((actnorm_bwd_kernel<1>), grid, dim3(256), 0, s, x, mask, logs, dz, dlogdet, x_len, dx, dlogs, dbias, B, C, T, nb);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_ACTNORM_BWD, B, C, T, 0, false, all_aligned16({x, mask, dz, dx}));
+    as_one_of<4, 1>(pl.width, [&](auto V) {
+        hipLaunchKernelGGL((actnorm_bwd_kernel<V>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, x, mask, logs, dz,
+                           dlogdet, x_len, dx, dlogs, dbias, B, C, T, pl.nb);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_actnorm_bwd");
 }
 
 extern "C" int glowtts_actnorm_stats(const float *x, const float *mask, float *sum_x, float *sum_x2, int B, int C,
                                      int T, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && sum_x && sum_x2, "glowtts_actnorm_stats: null pointer");
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0, "glowtts_actnorm_stats: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_ACTNORM_STATS, "glowtts_actnorm_stats", B, C, T, 0)) return rc;
     if ((long)B * C * T == 0) return 0;
-    const int nb = slab_size(B, C);
-    dim3 grid(C, (B + nb - 1) / nb);
-    if (can_vec4(T, {x, mask}))
-        hipLaunchKernelGGL((actnorm_stats_kernel<4>), grid, dim3(256), 0, (hipStream_t)stream, x, mask, sum_x, sum_x2, B, C, T, nb);
-    else
-        hipLaunchKernelGGL((actnorm_stats_kernel<1>), grid, dim3(256), 0, (hipStream_t)stream, x, mask, sum_x, sum_x2, B, C, T, nb);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_ACTNORM_STATS, B, C, T, 0, false, all_aligned16({x, mask}));
+    as_one_of<4, 1>(pl.width, [&](auto V) {
+        hipLaunchKernelGGL((actnorm_stats_kernel<V>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, x, mask, sum_x,
+                           sum_x2, B, C, T, pl.nb);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_actnorm_stats");
 }
 
@@ -1035,42 +1018,22 @@ extern "C" int glowtts_invconv_prepare_multi(const long long *w_table, float *w_
     GLOWTTS_LAUNCH_CHECK("glowtts_invconv_prepare_multi");
 }
 
-#define INVCONV_DISPATCH(KERNEL, GRID, ...)                                                              \
-    do {                                                                                                 \
-        if (n_split == 4) {                                                                              \
-            if (v4) hipLaunchKernelGGL((KERNEL<4, 4>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-            else    hipLaunchKernelGGL((KERNEL<4, 1>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-        } else if (n_split == 2) {                                                                       \
-            if (v4) hipLaunchKernelGGL((KERNEL<2, 4>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-            else    hipLaunchKernelGGL((KERNEL<2, 1>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-        } else {                                                                                         \
-            if (v4) hipLaunchKernelGGL((KERNEL<8, 4>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-            else    hipLaunchKernelGGL((KERNEL<8, 1>), GRID, dim3(256), 0, s, __VA_ARGS__);              \
-        }                                                                                                \
-    } while (0)
-
 extern "C" int glowtts_invconv_fwd(const float *x, const float *mask, const float *w, const float *logdet_w,
                                    const float *x_len, float *z, float *logdet, int B, int C, int T, int n_split,
                                    glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && w && z, "glowtts_invconv_fwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split >= 2 && n_split % 2 == 0 && n_split <= kInvConvMaxN,
-                      "glowtts_invconv_fwd: n_split=%d (supported: even values up to %d)", n_split, kInvConvMaxN);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0, "glowtts_invconv_fwd: C=%d not divisible by n_split=%d", C, n_split);
+    if (int rc = flow_check(GLOWTTS_FLOW_INVCONV_FWD, "glowtts_invconv_fwd", B, C, T, n_split)) return rc;
     GLOWTTS_CHECK_ARG(!logdet || (logdet_w && x_len), "glowtts_invconv_fwd: logdet requested without logdet_w/x_len");
     if ((long)B * C * T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, mask, z});
-    if (n_split != 2 && n_split != 4 && n_split != 8) {          // run-time N form
-        const long items = (long)B * C * (v4 ? T / 4 : T);
-        int gg = cdiv(items, 256);
-        if (gg > 4096) gg = 4096;
-        if (v4) hipLaunchKernelGGL((invconv_mix_generic_kernel<4, false>), dim3(gg), dim3(256), 0, s, x, mask, w, logdet_w, x_len, z, logdet, B, C, T, n_split);
-        else    hipLaunchKernelGGL((invconv_mix_generic_kernel<1, false>), dim3(gg), dim3(256), 0, s, x, mask, w, logdet_w, x_len, z, logdet, B, C, T, n_split);
-        GLOWTTS_LAUNCH_CHECK("glowtts_invconv_fwd");
-    }
-    const long n = (long)B * (C / n_split) * (v4 ? T / 4 : T);
-    dim3 grid(cdiv(n, 256));
-    INVCONV_DISPATCH(invconv_fwd_kernel, grid, x, mask, w, logdet_w, x_len, z, logdet, B, C, T);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_INVCONV_FWD, B, C, T, n_split, false, all_aligned16({x, mask, z}));
+    as_one_of<4, 1>(pl.width, [&](auto V) {
+        if (!as_one_of<2, 4, 8>(pl.n, [&](auto N) {
+                hipLaunchKernelGGL((invconv_fwd_kernel<N, V>), dim3(pl.grid_x), dim3(256), 0, s, x, mask, w, logdet_w, x_len, z, logdet, B, C, T);
+            }))                                                 // run-time N form
+            hipLaunchKernelGGL((invconv_mix_generic_kernel<V, false>), dim3(pl.grid_x), dim3(256), 0, s, x, mask, w, logdet_w, x_len, z,
+                               logdet, B, C, T, n_split);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_invconv_fwd");
 }
 
@@ -1078,32 +1041,21 @@ extern "C" int glowtts_invconv_bwd(const float *x, const float *mask, const floa
                                    const float *dz, const float *dlogdet, const float *x_len, float *dx, float *dw,
                                    int B, int C, int T, int n_split, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && w && dz && dx && dw, "glowtts_invconv_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split >= 2 && n_split % 2 == 0 && n_split <= kInvConvMaxN,
-                      "glowtts_invconv_bwd: n_split=%d (supported: even values up to %d)", n_split, kInvConvMaxN);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0, "glowtts_invconv_bwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_INVCONV_BWD, "glowtts_invconv_bwd", B, C, T, n_split)) return rc;
     GLOWTTS_CHECK_ARG(!dlogdet || (w_inv && x_len), "glowtts_invconv_bwd: dlogdet given without w_inv/x_len");
     if ((long)B * C * T == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, mask, dz, dx});
-    if (n_split != 2 && n_split != 4 && n_split != 8) {          // run-time N form: dx = W^T (dz mask), then dW entry by entry
-        const long items = (long)B * C * (v4 ? T / 4 : T);
-        int gg = cdiv(items, 256);
-        if (gg > 4096) gg = 4096;
-        const dim3 gw(n_split * n_split);
-        if (v4) {
-            hipLaunchKernelGGL((invconv_mix_generic_kernel<4, true>), dim3(gg), dim3(256), 0, s, dz, mask, w, nullptr, nullptr, dx, nullptr, B, C, T, n_split);
-            hipLaunchKernelGGL((invconv_dw_generic_kernel<4>), gw, dim3(256), 0, s, x, mask, w_inv, dz, dlogdet, x_len, dw, B, C, T, n_split);
-        } else {
-            hipLaunchKernelGGL((invconv_mix_generic_kernel<1, true>), dim3(gg), dim3(256), 0, s, dz, mask, w, nullptr, nullptr, dx, nullptr, B, C, T, n_split);
-            hipLaunchKernelGGL((invconv_dw_generic_kernel<1>), gw, dim3(256), 0, s, x, mask, w_inv, dz, dlogdet, x_len, dw, B, C, T, n_split);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_INVCONV_BWD, B, C, T, n_split, false, all_aligned16({x, mask, dz, dx}));
+    as_one_of<4, 1>(pl.width, [&](auto V) {
+        if (!as_one_of<2, 4, 8>(pl.n, [&](auto N) {
+                hipLaunchKernelGGL((invconv_bwd_kernel<N, V>), dim3(pl.grid_x), dim3(256), 0, s, x, mask, w, w_inv, dz, dlogdet, x_len, dx, dw, B, C, T);
+            })) {                                               // run-time N form: dx = W^T (dz mask), then dW entry by entry
+            hipLaunchKernelGGL((invconv_mix_generic_kernel<V, true>), dim3(pl.grid_x), dim3(256), 0, s, dz, mask, w, nullptr, nullptr, dx,
+                               nullptr, B, C, T, n_split);
+            hipLaunchKernelGGL((invconv_dw_generic_kernel<V>), dim3(pl.grid2_x), dim3(256), 0, s, x, mask, w_inv, dz, dlogdet, x_len, dw,
+                               B, C, T, n_split);
         }
-        GLOWTTS_LAUNCH_CHECK("glowtts_invconv_bwd");
-    }
-    const long n = (long)B * (C / n_split) * (v4 ? T / 4 : T);
-    int g = cdiv(n, 256);
-    if (g > 1024) g = 1024;
-    dim3 grid(g);
-    INVCONV_DISPATCH(invconv_bwd_kernel, grid, x, mask, w, w_inv, dz, dlogdet, x_len, dx, dw, B, C, T);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_invconv_bwd");
 }
 
@@ -1113,23 +1065,13 @@ extern "C" int glowtts_coupling_fwd_io(const void *x, const float *out, const fl
                                        int B, int C, int T, int sigmoid_scale, int reverse, int io, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && out && mask && z, "glowtts_coupling_fwd: null pointer");
     GLOWTTS_CHECK_ARG(reverse || logdet, "glowtts_coupling_fwd: forward needs logdet");
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && (C % 2) == 0 && T >= 0, "glowtts_coupling_fwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_COUPLING_FWD, "glowtts_coupling_fwd", B, C, T, 0)) return rc;
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, out, mask, z});
-    const long items = (long)(C / 2) * (v4 ? T / 4 : T);
-    int gx = cdiv(items, 256);
-    const int gmax = reverse ? 64 : 16;          // forward: one logdet[b] atomic per workgroup, same cache line for 16 b
-    if (gx > gmax) gx = gmax;
-    dim3 grid(gx, B);
-#define GLOWTTS_CPL(REV, B16)                                                                                                      \
-    do {                                                                                                                            \
-        if (v4) hipLaunchKernelGGL((coupling_fwd_kernel<4, REV, B16>), grid, dim3(256), 0, s, x, out, mask, z, logdet, C, T, sigmoid_scale); \
-        else    hipLaunchKernelGGL((coupling_fwd_kernel<1, REV, B16>), grid, dim3(256), 0, s, x, out, mask, z, logdet, C, T, sigmoid_scale); \
-    } while (0)
-    if (io) { if (reverse) GLOWTTS_CPL(true, true); else GLOWTTS_CPL(false, true); }
-    else    { if (reverse) GLOWTTS_CPL(true, false); else GLOWTTS_CPL(false, false); }
-#undef GLOWTTS_CPL
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_COUPLING_FWD, B, C, T, 0, reverse != 0, all_aligned16({x, out, mask, z}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_bool(reverse != 0, [&](auto REV) { as_bool(io != 0, [&](auto B16) {
+        hipLaunchKernelGGL((coupling_fwd_kernel<V, REV, B16>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, x, out, mask,
+                           z, logdet, C, T, sigmoid_scale);
+    }); }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_coupling_fwd");
 }
 
@@ -1142,24 +1084,15 @@ extern "C" int glowtts_coupling_bwd_io(const void *x, const float *out, const fl
                                        const float *dlogdet, void *dx, void *dout, int B, int C, int T,
                                        int sigmoid_scale, int io, int io_dout, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && out && mask && dz && dx && dout, "glowtts_coupling_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && (C % 2) == 0 && T >= 0, "glowtts_coupling_bwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_COUPLING_BWD, "glowtts_coupling_bwd", B, C, T, 0)) return rc;
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, out, mask, dz, dx, dout});
-    const long items = (long)(C / 2) * (v4 ? T / 4 : T);
-    int gx = cdiv(items, 256);
-    if (gx > 64) gx = 64;
-    dim3 grid(gx, B);
     GLOWTTS_CHECK_ARG(!io || io_dout, "glowtts_coupling_bwd: bf16 flow tensors go with a bf16 dout");
-#define GLOWTTS_CPB(B16, D16)                                                                                                       \
-    do {                                                                                                                             \
-        if (v4) hipLaunchKernelGGL((coupling_bwd_kernel<4, B16, D16>), grid, dim3(256), 0, s, x, out, mask, dz, dlogdet, dx, dout, C, T, sigmoid_scale); \
-        else    hipLaunchKernelGGL((coupling_bwd_kernel<1, B16, D16>), grid, dim3(256), 0, s, x, out, mask, dz, dlogdet, dx, dout, C, T, sigmoid_scale); \
-    } while (0)
-    if (io) GLOWTTS_CPB(true, true);
-    else if (io_dout) GLOWTTS_CPB(false, true);
-    else GLOWTTS_CPB(false, false);
-#undef GLOWTTS_CPB
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_COUPLING_BWD, B, C, T, 0, false, all_aligned16({x, out, mask, dz, dx, dout}));
+    // the three forms that exist: 0 = all fp32, 1 = bf16 dout, 2 = bf16 flow tensors and dout
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_one_of<0, 1, 2>(io ? 2 : io_dout ? 1 : 0, [&](auto F) {
+        hipLaunchKernelGGL((coupling_bwd_kernel<V, F == 2, F >= 1>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, x, out,
+                           mask, dz, dlogdet, dx, dout, C, T, sigmoid_scale);
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_coupling_bwd");
 }
 
@@ -1169,36 +1102,19 @@ extern "C" int glowtts_coupling_bwd(const float *x, const float *out, const floa
     return glowtts_coupling_bwd_io(x, out, mask, dz, dlogdet, dx, dout, B, C, T, sigmoid_scale, 0, 0, stream);
 }
 
-#define FUSED_DISPATCH_T(KERNEL, B16, GRID, ...)                                                        \
-    do {                                                                                                \
-        if (n_split == 4) {                                                                             \
-            if (v4) hipLaunchKernelGGL((KERNEL<4, 4, B16>), GRID, dim3(256), 0, s, __VA_ARGS__);        \
-            else    hipLaunchKernelGGL((KERNEL<4, 1, B16>), GRID, dim3(256), 0, s, __VA_ARGS__);        \
-        } else {                                                                                        \
-            if (v4) hipLaunchKernelGGL((KERNEL<2, 4, B16>), GRID, dim3(256), 0, s, __VA_ARGS__);        \
-            else    hipLaunchKernelGGL((KERNEL<2, 1, B16>), GRID, dim3(256), 0, s, __VA_ARGS__);        \
-        }                                                                                               \
-    } while (0)
-#define FUSED_DISPATCH(KERNEL, GRID, ...)                                                               \
-    do {                                                                                                \
-        if (io) FUSED_DISPATCH_T(KERNEL, true, GRID, __VA_ARGS__);                                      \
-        else    FUSED_DISPATCH_T(KERNEL, false, GRID, __VA_ARGS__);                                     \
-    } while (0)
-
 extern "C" int glowtts_actnorm_invconv_fwd_io(const void *x, const float *mask, const float *logs, const float *bias,
                                               const float *w, const float *logdet_w, const float *x_len, void *z,
                                               float *logdet, void *z0h, int B, int C, int T, int n_split, int io,
                                               glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && logs && bias && w && z, "glowtts_actnorm_invconv_fwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split == 2 || n_split == 4, "glowtts_actnorm_invconv_fwd: n_split=%d (fused path: 2 or 4)", n_split);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0, "glowtts_actnorm_invconv_fwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_ACTNORM_INVCONV_FWD, "glowtts_actnorm_invconv_fwd", B, C, T, n_split)) return rc;
     GLOWTTS_CHECK_ARG(!logdet || (logdet_w && x_len), "glowtts_actnorm_invconv_fwd: logdet requested without logdet_w/x_len");
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, mask, z});
-    const long n = (long)B * (C / n_split) * (v4 ? T / 4 : T);
-    dim3 grid(cdiv(n, 256));
-    FUSED_DISPATCH(actnorm_invconv_fwd_kernel, grid, x, mask, logs, bias, w, logdet_w, x_len, z, logdet, B, C, T, z0h);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_ACTNORM_INVCONV_FWD, B, C, T, n_split, false, all_aligned16({x, mask, z}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_one_of<2, 4>(pl.n, [&](auto N) { as_bool(io != 0, [&](auto B16) {
+        hipLaunchKernelGGL((actnorm_invconv_fwd_kernel<N, V, B16>), dim3(pl.grid_x), dim3(256), 0, (hipStream_t)stream, x, mask, logs, bias,
+                           w, logdet_w, x_len, z, logdet, B, C, T, z0h);
+    }); }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_actnorm_invconv_fwd");
 }
 
@@ -1213,21 +1129,14 @@ extern "C" int glowtts_actnorm_invconv_bwd_io(const void *x, const float *mask, 
                                               const float *x_len, void *dx, float *dlogs, float *dbias, float *dw, int B,
                                               int C, int T, int n_split, int io, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(x && mask && logs && bias && w && dz && dx && dlogs && dbias && dw, "glowtts_actnorm_invconv_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split == 2 || n_split == 4, "glowtts_actnorm_invconv_bwd: n_split=%d (fused path: 2 or 4)", n_split);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0, "glowtts_actnorm_invconv_bwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_ACTNORM_INVCONV_BWD, "glowtts_actnorm_invconv_bwd", B, C, T, n_split)) return rc;
     GLOWTTS_CHECK_ARG(!dlogdet || (w_inv && x_len), "glowtts_actnorm_invconv_bwd: dlogdet given without w_inv/x_len");
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, mask, dz, dx});
-    const int G = C / n_split;
-    const long items = (long)B * (v4 ? T / 4 : T);                       // per channel group
-    long slabs = (200 + G - 1) / G;     // ~200 workgroups (see the kernel's comment; 80 / 120 / 160 / 200 / 288 / 400 / 520 at
-                                        // B=32, C=160, T=400: 10.9 / 9.5 / 9.1 / 8.9 / 9.6 / 10.6 / 11.7 us)
-    if (slabs > (items + 255) / 256) slabs = (items + 255) / 256;
-    if (slabs < 1) slabs = 1;
-    const int nb = (int)((items + slabs - 1) / slabs);
-    dim3 grid(G, (unsigned)((items + nb - 1) / nb));
-    FUSED_DISPATCH(actnorm_invconv_bwd_kernel, grid, x, mask, logs, bias, w, w_inv, dz, dlogdet, x_len, dx, dlogs, dbias, dw, B, C, T, nb);
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_ACTNORM_INVCONV_BWD, B, C, T, n_split, false, all_aligned16({x, mask, dz, dx}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_one_of<2, 4>(pl.n, [&](auto N) { as_bool(io != 0, [&](auto B16) {
+        hipLaunchKernelGGL((actnorm_invconv_bwd_kernel<N, V, B16>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, x, mask,
+                           logs, bias, w, w_inv, dz, dlogdet, x_len, dx, dlogs, dbias, dw, B, C, T, pl.nb);
+    }); }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_actnorm_invconv_bwd");
 }
 
@@ -1246,25 +1155,14 @@ extern "C" int glowtts_coupling_actnorm_invconv_fwd(const float *y_prev, const f
                                                     int sigmoid_scale, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(y_prev && out_prev && mask && logs && bias && w && logdet_w && x_len && y && logdet_prev && logdet,
                       "glowtts_coupling_actnorm_invconv_fwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split == 2 || n_split == 4, "glowtts_coupling_actnorm_invconv_fwd: n_split=%d (fused path: 2 or 4)", n_split);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0 && C % 2 == 0, "glowtts_coupling_actnorm_invconv_fwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_FWD, "glowtts_coupling_actnorm_invconv_fwd", B, C, T, n_split)) return rc;
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {y_prev, out_prev, mask, y});
-    const long items = (long)(C / n_split) * (v4 ? T / 4 : T);
-    int gx = cdiv(items, 256);
-    if (gx > 8) gx = 8;                                 // one logdet_prev[b] atomic per workgroup; 8 x B workgroups of ~2 items per
-                                                        // thread: 7.3 us at config 2 where 16 x B (one item per thread) took 8.9
-    dim3 grid(gx, B);
-#define GLOWTTS_CAF(NN)                                                                                                          \
-    do {                                                                                                                          \
-        if (v4) hipLaunchKernelGGL((coupling_ai_fwd_kernel<NN, 4>), grid, dim3(256), 0, s, y_prev, out_prev, mask, logs, bias, w, \
-                                   logdet_w, x_len, y, logdet_prev, logdet, B, C, T, sigmoid_scale);                              \
-        else    hipLaunchKernelGGL((coupling_ai_fwd_kernel<NN, 1>), grid, dim3(256), 0, s, y_prev, out_prev, mask, logs, bias, w, \
-                                   logdet_w, x_len, y, logdet_prev, logdet, B, C, T, sigmoid_scale);                              \
-    } while (0)
-    if (n_split == 4) GLOWTTS_CAF(4); else GLOWTTS_CAF(2);
-#undef GLOWTTS_CAF
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_FWD, B, C, T, n_split, false,
+                                  all_aligned16({y_prev, out_prev, mask, y}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_one_of<2, 4>(pl.n, [&](auto N) {
+        hipLaunchKernelGGL((coupling_ai_fwd_kernel<N, V>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, y_prev, out_prev,
+                           mask, logs, bias, w, logdet_w, x_len, y, logdet_prev, logdet, B, C, T, sigmoid_scale);
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_coupling_actnorm_invconv_fwd");
 }
 
@@ -1275,28 +1173,15 @@ extern "C" int glowtts_coupling_actnorm_invconv_bwd(const float *y_prev, const f
                                                     int sigmoid_scale, glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(y_prev && out_prev && mask && logs && bias && w && dz && dy_prev && dout_prev && dlogs && dbias && dw,
                       "glowtts_coupling_actnorm_invconv_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_split == 2 || n_split == 4, "glowtts_coupling_actnorm_invconv_bwd: n_split=%d (fused path: 2 or 4)", n_split);
-    GLOWTTS_CHECK_ARG(B >= 0 && C > 0 && T >= 0 && C % n_split == 0 && C % 2 == 0, "glowtts_coupling_actnorm_invconv_bwd: bad shape");
+    if (int rc = flow_check(GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_BWD, "glowtts_coupling_actnorm_invconv_bwd", B, C, T, n_split)) return rc;
     GLOWTTS_CHECK_ARG(!dlogdet || (w_inv && x_len), "glowtts_coupling_actnorm_invconv_bwd: dlogdet given without w_inv/x_len");
     if ((long)B * C * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {y_prev, out_prev, mask, dz, dy_prev, dout_prev});
-    const int G = C / n_split;
-    const int items = B * (v4 ? T / 4 : T);
-    int slabs = (200 + G - 1) / G;                      // (120 .. 800 workgroups measured: 200 is the fastest, 13.2 us at config 2)
-    const int max_slabs = (items + 255) / 256;
-    if (slabs > max_slabs) slabs = max_slabs;
-    if (slabs < 1) slabs = 1;
-    const int nb = (items + slabs - 1) / slabs;
-    dim3 grid(G, (items + nb - 1) / nb);
-#define GLOWTTS_CAB(NN)                                                                                                            \
-    do {                                                                                                                            \
-        if (v4) hipLaunchKernelGGL((coupling_ai_bwd_kernel<NN, 4>), grid, dim3(256), 0, s, y_prev, out_prev, mask, logs, bias, w, w_inv, \
-                                   dz, dlogdet, x_len, dy_prev, dout_prev, dlogs, dbias, dw, B, C, T, nb, sigmoid_scale);             \
-        else    hipLaunchKernelGGL((coupling_ai_bwd_kernel<NN, 1>), grid, dim3(256), 0, s, y_prev, out_prev, mask, logs, bias, w, w_inv, \
-                                   dz, dlogdet, x_len, dy_prev, dout_prev, dlogs, dbias, dw, B, C, T, nb, sigmoid_scale);             \
-    } while (0)
-    if (n_split == 4) GLOWTTS_CAB(4); else GLOWTTS_CAB(2);
-#undef GLOWTTS_CAB
+    const FlowPlan pl = plan_flow(GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_BWD, B, C, T, n_split, false,
+                                  all_aligned16({y_prev, out_prev, mask, dz, dy_prev, dout_prev}));
+    as_one_of<4, 1>(pl.width, [&](auto V) { as_one_of<2, 4>(pl.n, [&](auto N) {
+        hipLaunchKernelGGL((coupling_ai_bwd_kernel<N, V>), dim3(pl.grid_x, pl.grid_y), dim3(256), 0, (hipStream_t)stream, y_prev, out_prev,
+                           mask, logs, bias, w, w_inv, dz, dlogdet, x_len, dy_prev, dout_prev, dlogs, dbias, dw, B, C, T, pl.nb,
+                           sigmoid_scale);
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_coupling_actnorm_invconv_bwd");
 }

@@ -164,15 +164,17 @@ __global__ __launch_bounds__(256) void res_skip_bwd_kernel(const void *__restric
 
 using namespace glowtts;
 
+// Every launch here is one thread per (b, c < H, t-vector): ceil(B H T / width / 256) workgroups
+static inline dim3 wn_grid(int B, int H, int T, int width) { return dim3(cdiv((long)B * H * (T / width), 256)); }
+
 extern "C" int glowtts_gate_fwd(const float *a, const float *g, float *acts, int B, int H, int T,
                                 glowtts_stream_t stream) {
     GLOWTTS_CHECK_ARG(a && acts, "glowtts_gate_fwd: null pointer");
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0, "glowtts_gate_fwd: bad shape");
     if ((long)B * H * T == 0) return 0;
-    const bool v4 = can_vec4(T, {a, acts});
-    const long n = (long)B * H * (v4 ? T / 4 : T);
-    if (v4) hipLaunchKernelGGL((gate_fwd_kernel<4>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a, g, acts, B, H, T);
-    else    hipLaunchKernelGGL((gate_fwd_kernel<1>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a, g, acts, B, H, T);
+    as_one_of<4, 1>(can_vec4(T, {a, acts}) ? 4 : 1, [&](auto V) {
+        hipLaunchKernelGGL((gate_fwd_kernel<V>), wn_grid(B, H, T, V), dim3(256), 0, (hipStream_t)stream, a, g, acts, B, H, T);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_gate_fwd");
 }
 
@@ -181,10 +183,9 @@ extern "C" int glowtts_gate_bwd(const float *a, const float *g, const float *dac
     GLOWTTS_CHECK_ARG(a && dacts && da, "glowtts_gate_bwd: null pointer");
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0, "glowtts_gate_bwd: bad shape");
     if ((long)B * H * T == 0) return 0;
-    const bool v4 = can_vec4(T, {a, dacts, da});
-    const long n = (long)B * H * (v4 ? T / 4 : T);
-    if (v4) hipLaunchKernelGGL((gate_bwd_kernel<4>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a, g, dacts, da, B, H, T);
-    else    hipLaunchKernelGGL((gate_bwd_kernel<1>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, a, g, dacts, da, B, H, T);
+    as_one_of<4, 1>(can_vec4(T, {a, dacts, da}) ? 4 : 1, [&](auto V) {
+        hipLaunchKernelGGL((gate_bwd_kernel<V>), wn_grid(B, H, T, V), dim3(256), 0, (hipStream_t)stream, a, g, dacts, da, B, H, T);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_gate_bwd");
 }
 
@@ -193,10 +194,10 @@ extern "C" int glowtts_gate_bwd_ts(const float *ts, const float *dacts, const un
     GLOWTTS_CHECK_ARG(ts && dacts && da, "glowtts_gate_bwd_ts: null pointer");
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0, "glowtts_gate_bwd_ts: bad shape");
     if ((long)B * H * T == 0) return 0;
-    const bool v4 = can_vec4(T, {ts, dacts, da});
-    const long n = (long)B * H * (v4 ? T / 4 : T);
-    if (v4) hipLaunchKernelGGL((gate_bwd_ts_kernel<4>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, ts, dacts, drop, drop_scale, da, B, H, T);
-    else    hipLaunchKernelGGL((gate_bwd_ts_kernel<1>), dim3(cdiv(n, 256)), dim3(256), 0, (hipStream_t)stream, ts, dacts, drop, drop_scale, da, B, H, T);
+    as_one_of<4, 1>(can_vec4(T, {ts, dacts, da}) ? 4 : 1, [&](auto V) {
+        hipLaunchKernelGGL((gate_bwd_ts_kernel<V>), wn_grid(B, H, T, V), dim3(256), 0, (hipStream_t)stream, ts, dacts, drop, drop_scale, da,
+                           B, H, T);
+    });
     GLOWTTS_LAUNCH_CHECK("glowtts_gate_bwd_ts");
 }
 
@@ -207,17 +208,10 @@ extern "C" int glowtts_res_skip_fwd(const float *x, const float *rs, const float
     GLOWTTS_CHECK_ARG(last || (x && x_out), "glowtts_res_skip_fwd: x / x_out required unless last");
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0, "glowtts_res_skip_fwd: bad shape");
     if ((long)B * H * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {x, rs, mask, skip_in, x_out, skip_out});
-    const long n = (long)B * H * (v4 ? T / 4 : T);
-    dim3 grid(cdiv(n, 256));
-    if (last) {
-        if (v4) hipLaunchKernelGGL((res_skip_fwd_kernel<4, true>), grid, dim3(256), 0, s, x, rs, mask, skip_in, x_out, skip_out, B, H, T);
-        else    hipLaunchKernelGGL((res_skip_fwd_kernel<1, true>), grid, dim3(256), 0, s, x, rs, mask, skip_in, x_out, skip_out, B, H, T);
-    } else {
-        if (v4) hipLaunchKernelGGL((res_skip_fwd_kernel<4, false>), grid, dim3(256), 0, s, x, rs, mask, skip_in, x_out, skip_out, B, H, T);
-        else    hipLaunchKernelGGL((res_skip_fwd_kernel<1, false>), grid, dim3(256), 0, s, x, rs, mask, skip_in, x_out, skip_out, B, H, T);
-    }
+    as_one_of<4, 1>(can_vec4(T, {x, rs, mask, skip_in, x_out, skip_out}) ? 4 : 1, [&](auto V) { as_bool(last != 0, [&](auto LAST) {
+        hipLaunchKernelGGL((res_skip_fwd_kernel<V, LAST>), wn_grid(B, H, T, V), dim3(256), 0, (hipStream_t)stream, x, rs, mask, skip_in,
+                           x_out, skip_out, B, H, T);
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_res_skip_fwd");
 }
 
@@ -227,18 +221,12 @@ extern "C" int glowtts_res_skip_bwd_io(const void *dx_out, const void *dskip, co
     GLOWTTS_CHECK_ARG(last || dx_out, "glowtts_res_skip_bwd: dx_out required unless last");
     GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0, "glowtts_res_skip_bwd: bad shape");
     if ((long)B * H * T == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    const bool v4 = can_vec4(T, {dx_out, dskip, mask, dx, drs});
-    const long n = (long)B * H * (v4 ? T / 4 : T);
-    dim3 grid(cdiv(n, 256));
-#define GLOWTTS_RSB(LAST, B16)                                                                                                     \
-    do {                                                                                                                            \
-        if (v4) hipLaunchKernelGGL((res_skip_bwd_kernel<4, LAST, B16>), grid, dim3(256), 0, s, dx_out, dskip, mask, dx, drs, B, H, T); \
-        else    hipLaunchKernelGGL((res_skip_bwd_kernel<1, LAST, B16>), grid, dim3(256), 0, s, dx_out, dskip, mask, dx, drs, B, H, T); \
-    } while (0)
-    if (io) { if (last) GLOWTTS_RSB(true, true); else GLOWTTS_RSB(false, true); }
-    else    { if (last) GLOWTTS_RSB(true, false); else GLOWTTS_RSB(false, false); }
-#undef GLOWTTS_RSB
+    as_one_of<4, 1>(can_vec4(T, {dx_out, dskip, mask, dx, drs}) ? 4 : 1, [&](auto V) { as_bool(last != 0, [&](auto LAST) {
+        as_bool(io != 0, [&](auto B16) {
+            hipLaunchKernelGGL((res_skip_bwd_kernel<V, LAST, B16>), wn_grid(B, H, T, V), dim3(256), 0, (hipStream_t)stream, dx_out, dskip,
+                               mask, dx, drs, B, H, T);
+        });
+    }); });
     GLOWTTS_LAUNCH_CHECK("glowtts_res_skip_bwd");
 }
 

@@ -313,6 +313,38 @@ int glowtts_coupling_bwd(const float *x, const float *out, const float *mask, co
                          const float *dlogdet, float *dx, float *dout, int B, int C, int T, int sigmoid_scale,
                          glowtts_stream_t stream);
 
+/* ---- what would this flow call launch?  (no reference counterpart; csrc/flow_plan.hpp) ---------------------------------------
+ * The decision the entry point behind `op` (GLOWTTS_FLOW_* below; the `_io` forms decide alike) makes for a (B, C, T) tensor — a
+ * pure host function: it touches no device and works on a machine without a GPU.  n_split is read by the InvConv and fused
+ * operations, reverse by actnorm_fwd and coupling_fwd; aligned = 1: every tensor the vector kernels touch starts on a 16-byte
+ * boundary.  Non-zero (and glowtts_last_error) for the shapes that call rejects.  An empty tensor: all zero (nothing is launched).
+ *   width    : floats per access along T: 4 (T % 4 == 0 and aligned) or 1
+ *   n        : the group size compiled into the kernel (2, 4, 8; the fused operations 2, 4); 0: the run-time-N kernels of
+ *              InvConv, and the operations without channel groups
+ *   grid_x/y : the grid of the (first) launch, 256 threads per workgroup
+ *   nb       : what a workgroup row takes, where the kernel is told: utterances (actnorm_bwd, actnorm_stats), items of the
+ *              flattened (b, t / width) axis (the two fused backward operations); else 0
+ *   launches : kernel launches of the call: 2 for invconv_bwd on the run-time-N kernels (dx, then dW), else 1
+ *   grid2_x  : the grid of that second launch (n_split^2 workgroups, one per entry of dW), else 0 */
+#define GLOWTTS_FLOW_ACTNORM_FWD 1
+#define GLOWTTS_FLOW_ACTNORM_BWD 2
+#define GLOWTTS_FLOW_ACTNORM_STATS 3
+#define GLOWTTS_FLOW_INVCONV_FWD 4
+#define GLOWTTS_FLOW_INVCONV_BWD 5
+#define GLOWTTS_FLOW_ACTNORM_INVCONV_FWD 6
+#define GLOWTTS_FLOW_ACTNORM_INVCONV_BWD 7
+#define GLOWTTS_FLOW_COUPLING_FWD 8
+#define GLOWTTS_FLOW_COUPLING_BWD 9
+#define GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_FWD 10
+#define GLOWTTS_FLOW_COUPLING_ACTNORM_INVCONV_BWD 11
+typedef struct glowtts_flow_plan {
+    int32_t width, n;
+    int32_t grid_x, grid_y;
+    int32_t nb;
+    int32_t launches, grid2_x;
+} glowtts_flow_plan;
+int glowtts_flow_plan_for(int op, int B, int C, int T, int n_split, int reverse, int aligned, glowtts_flow_plan *out);
+
 /* ---- WN gate (utils.py:31-38) and residual/skip update (layers.py:157-161) ----------------------------------
  * gate fwd: acts[b,c,t] = tanh(a[b,c,t] + g[b,c]) * sigmoid(a[b,H+c,t] + g[b,H+c]) ; a (B,2H,T), g (B,2H) or NULL
  * gate bwd: da (B,2H,T) from dacts (B,H,T); the activations are recomputed from a, g (nothing else is saved).

@@ -63,7 +63,9 @@ Two kinds of input.
        * invconv_prepare works in fp64 internally, so its bound is derived: |w_inv - inv64| <= 2**-24 |inv64| + 1e-9 max|inv64|,
          |logdet - logdet64| <= 2**-24 |logdet64| + 1e-9, for cond <= 100 (asserted for every matrix) and n <= 32.
 
-Shapes (B, C, T): the smallest that take each branch of the launchers at the end of flows.hip; each says which.
+Shapes (B, C, T): the smallest that take each branch of the launchers at the end of flows.hip; each says which, in prose and as
+the fields of the plan the library hands back (glowtts_flow_plan_for, csrc/flow_plan.hpp): section 9 asks it on the CPU, for every
+row and every shape, and compares it over a sweep with _parent_rules, the launch rules as the launchers had them inline.
 """
 import functools
 import math
@@ -567,8 +569,14 @@ def _all_shapes(n):
 
 
 def _own(cases):
-    """A kernel's own shapes: [(shape, n_split, the branch it is there for)]."""
-    return [pytest.param(shape, n, id="x".join(map(str, shape)) + f"-n{n}") for shape, n, _why in cases]
+    """A kernel's own shapes: [(shape, n_split, the branch it is there for, what the library plans there)]."""
+    return [pytest.param(shape, n, id="x".join(map(str, shape)) + f"-n{n}") for shape, n, _why, _plan_ in cases]
+
+
+def _plan(ops, **fields):
+    """What a row's prose claims, as fields of glowtts_flow_plan (and of _parent_rules' extras: items, uncapped, last) for each
+    of `ops` ("coupling_fwd:rev": the reverse direction); test_plans_of_the_rows asks the library on the CPU."""
+    return {op: fields for op in ops}
 
 
 def _is_vec_shape(shape):
@@ -587,8 +595,10 @@ def test_mask_len(G, shape):
     print(f"mask_len {shape}: ==")
 
 
-SLAB = [((5, 1000, 12), 0, "slab_size: nbk = 3, nb = 2: three slabs of utterances, the last holds one"),
-        ((3, 2100, 101), 0, "one slab of 303 items > 256: the item loop of a workgroup wraps")]
+SLAB = [((5, 1000, 12), 0, "slab_size: nbk = 3, nb = 2: three slabs of utterances, the last holds one",
+         _plan(("actnorm_bwd", "actnorm_stats"), width=4, grid_x=1000, grid_y=3, nb=2, last=1)),
+        ((3, 2100, 101), 0, "one slab of 303 items > 256: the item loop of a workgroup wraps",
+         _plan(("actnorm_bwd", "actnorm_stats"), width=1, grid_x=2100, grid_y=1, nb=3, items=303))]
 
 
 @gpu
@@ -623,8 +633,11 @@ def test_actnorm_stats(G, shape, n):
 
 
 # =============================================================================================== 2. InvConvNear
-IC_BWD = [((4, 8, 16387), 2, "262192 items > 1024 x 256: the grid-stride loop of invconv_bwd_kernel runs twice, the second pass partial")]
-IC_GEN = [((2, 12, 43691), 6, "1048584 items > 4096 x 256: the workgroup cap of invconv_mix_generic_kernel")]
+IC_BWD = [((4, 8, 16387), 2, "262192 items > 1024 x 256: the grid-stride loop of invconv_bwd_kernel runs twice, the second pass partial",
+           _plan(("invconv_bwd",), width=1, n=2, items=262192, uncapped=1025, grid_x=1024, grid_y=1, launches=1))]
+IC_GEN = [((2, 12, 43691), 6, "1048584 items > 4096 x 256: the workgroup cap of invconv_mix_generic_kernel",
+           {**_plan(("invconv_fwd",), width=1, n=0, items=1048584, uncapped=4097, grid_x=4096, grid_y=1, launches=1, grid2_x=0),
+            **_plan(("invconv_bwd",), width=1, n=0, items=1048584, uncapped=4097, grid_x=4096, grid_y=1, launches=2, grid2_x=36)})]
 IC_SHAPES = [p for n in (2, 4, 8, 6, 32) for p in _all_shapes(n)]
 
 
@@ -643,13 +656,20 @@ def test_invconv_bwd(G, shape, n):
 
 
 # =============================================================================================== 3. ActNorm + InvConvNear fused
-FUSED_BWD = [((3, 8, 37), 4, "111 items: one slab, most threads idle"),
-             ((3, 8, 1001), 4, "G = 2: 12 slabs of 251 items, the last of 242; slab boundaries inside utterances"),
-             ((2, 400, 1001), 4, "G = 100: 2 slabs of 1001 items: four iterations per thread, the last partial (the prefetch hand-over)"),
-             ((70, 8, 5), 4, "B > 64: wave 3's dlogdet * x_len loop"),
-             ((3, 8, 1204), 4, "T % 4 == 0, the vector kernels: 903 items, 4 slabs of 226, the last of 225; boundaries inside utterances"),
+_FB = ("actnorm_invconv_bwd", "coupling_ai_bwd")
+FUSED_BWD = [((3, 8, 37), 4, "111 items: one slab, most threads idle",
+              _plan(_FB, width=1, n=4, grid_x=2, items=111, grid_y=1, nb=111, last=111)),
+             ((3, 8, 1001), 4, "G = 2: 12 slabs of 251 items, the last of 242; slab boundaries inside utterances",
+              _plan(_FB, width=1, n=4, grid_x=2, items=3003, grid_y=12, nb=251, last=242)),
+             ((2, 400, 1001), 4, "G = 100: 2 slabs of 1001 items: four iterations per thread, the last partial (the prefetch hand-over)",
+              _plan(_FB, width=1, n=4, grid_x=100, items=2002, grid_y=2, nb=1001, last=1001)),
+             ((70, 8, 5), 4, "B > 64: wave 3's dlogdet * x_len loop",
+              _plan(_FB, width=1, n=4, grid_x=2, items=350, grid_y=2, nb=175, last=175)),
+             ((3, 8, 1204), 4, "T % 4 == 0, the vector kernels: 903 items, 4 slabs of 226, the last of 225; boundaries inside utterances",
+              _plan(_FB, width=4, n=4, grid_x=2, items=903, grid_y=4, nb=226, last=225)),
              ((2, 400, 1032), 2, "T % 4 == 0, G = 200: one slab of 516 vector items: three iterations per thread, the last partial "
-                                 "(the prefetch hand-over of the vector kernels)")]
+                                 "(the prefetch hand-over of the vector kernels)",
+              _plan(_FB, width=4, n=2, grid_x=200, items=516, grid_y=1, nb=516, last=516))]
 FUSED_SHAPES = [p for n in (2, 4) for p in _all_shapes(n)]
 
 
@@ -667,9 +687,12 @@ def test_actnorm_invconv_bwd(G, shape, n):
 
 
 # =============================================================================================== 4. affine coupling
-CPL_FWD = [((2, 8, 1027), 0, "forward: 4108 items > 16 x 256 workgroups per utterance"),
-           ((2, 8, 4099), 0, "reverse: 16396 items > 64 x 256")]
-CPL_BWD = [((2, 8, 4099), 0, "16396 items > 64 x 256 workgroups per utterance")]
+CPL_FWD = [((2, 8, 1027), 0, "forward: 4108 items > 16 x 256 workgroups per utterance",
+            _plan(("coupling_fwd",), width=1, items=4108, uncapped=17, grid_x=16, grid_y=2)),
+           ((2, 8, 4099), 0, "reverse: 16396 items > 64 x 256",
+            _plan(("coupling_fwd:rev",), width=1, items=16396, uncapped=65, grid_x=64, grid_y=2))]
+CPL_BWD = [((2, 8, 4099), 0, "16396 items > 64 x 256 workgroups per utterance",
+            _plan(("coupling_bwd",), width=1, items=16396, uncapped=65, grid_x=64, grid_y=2))]
 CPL_ALL = _all_shapes(0)
 
 
@@ -689,7 +712,8 @@ def test_coupling_bwd(G, shape, n):
 
 
 # =============================================================================================== 5. coupling + ActNorm + InvConvNear
-CA_FWD = [((2, 8, 1027), 4, "2054 items > 8 x 256 workgroups per utterance")]
+CA_FWD = [((2, 8, 1027), 4, "2054 items > 8 x 256 workgroups per utterance",
+           _plan(("coupling_ai_fwd",), width=1, n=4, items=2054, uncapped=9, grid_x=8, grid_y=2))]
 
 
 @gpu
@@ -905,3 +929,208 @@ def test_counting_matrices_tell_w_from_its_inverse_and_transpose():
         assert torch.equal(w.double() @ inv.double(), torch.eye(n, dtype=torch.float64))
         assert not torch.equal(w, w.T) and not torch.equal(w, inv) and not torch.equal(w, inv.T) and not torch.equal(inv, inv.T)
         assert abs(abs(float(torch.det(w.double()))) - 1.0) < 1e-9
+
+
+# =============================================================================================== 9. what the library plans, on the CPU
+PLAN_FIELDS = ("width", "n", "grid_x", "grid_y", "nb", "launches", "grid2_x")
+PLAN_OPS = {"actnorm_fwd": "ACTNORM_FWD", "actnorm_bwd": "ACTNORM_BWD", "actnorm_stats": "ACTNORM_STATS", "invconv_fwd": "INVCONV_FWD",
+            "invconv_bwd": "INVCONV_BWD", "actnorm_invconv_fwd": "ACTNORM_INVCONV_FWD", "actnorm_invconv_bwd": "ACTNORM_INVCONV_BWD",
+            "coupling_fwd": "COUPLING_FWD", "coupling_bwd": "COUPLING_BWD", "coupling_ai_fwd": "COUPLING_ACTNORM_INVCONV_FWD",
+            "coupling_ai_bwd": "COUPLING_ACTNORM_INVCONV_BWD"}
+_IC_OPS, _FUSED_OPS = ("invconv_fwd", "invconv_bwd"), ("actnorm_invconv_fwd", "actnorm_invconv_bwd", "coupling_ai_fwd", "coupling_ai_bwd")
+
+
+def _parent_rules(op, B, C, T, n, rev, aligned):
+    """What the launcher behind `op` decided while the rules stood inline in the launchers of flows.hip (the commit before
+    csrc/flow_plan.hpp), restated from those launchers: None where the entry point rejects the shape, else (the plan's fields in
+    the order of PLAN_FIELDS, {items, uncapped, last}: the figures the rows' prose speaks of)."""
+    cdiv = lambda a, b: -(-a // b)
+    if op in _IC_OPS and not (n >= 2 and n % 2 == 0 and n <= 32):
+        return None
+    if op in _FUSED_OPS and n not in (2, 4):
+        return None
+    if not (B >= 0 and C > 0 and T >= 0) or (op in _IC_OPS + _FUSED_OPS and C % n) or (op.startswith("coupling") and C % 2):
+        return None
+    if B * C * T == 0:
+        return (0,) * 7, {}
+    v4 = bool(aligned) and T % 4 == 0                        # can_vec4
+    TV = T // 4 if v4 else T
+    nn, gx, gy, nb, launches, g2, ex = 0, 0, 1, 0, 1, 0, {}
+    if op == "actnorm_fwd":
+        gx = cdiv(B * C * TV, 256)
+    elif op in ("actnorm_bwd", "actnorm_stats"):             # slab_size
+        nbk = max(1, min(B, cdiv(2048, C)))
+        nb = cdiv(B, nbk)
+        gx, gy = C, cdiv(B, nb)
+        ex = dict(items=nb * TV, last=B - (gy - 1) * nb)
+    elif op in _IC_OPS:
+        if n in (2, 4, 8):
+            nn, items = n, B * (C // n) * TV
+            gx = cdiv(items, 256)
+            if op == "invconv_bwd":
+                gx = min(gx, 1024)
+        else:
+            items = B * C * TV
+            gx = min(cdiv(items, 256), 4096)
+            if op == "invconv_bwd":
+                launches, g2 = 2, n * n
+        ex = dict(items=items, uncapped=cdiv(items, 256))
+    elif op == "actnorm_invconv_fwd":
+        nn, gx = n, cdiv(B * (C // n) * TV, 256)
+    elif op in ("actnorm_invconv_bwd", "coupling_ai_bwd"):   # ~200 workgroups
+        G, items = C // n, B * TV
+        slabs = max(1, min(cdiv(200, G), cdiv(items, 256)))
+        nb = cdiv(items, slabs)
+        nn, gx, gy = n, G, cdiv(items, nb)
+        ex = dict(items=items, last=items - (gy - 1) * nb)
+    elif op in ("coupling_fwd", "coupling_bwd", "coupling_ai_fwd"):
+        items = (C // n if op == "coupling_ai_fwd" else C // 2) * TV
+        cap = 8 if op == "coupling_ai_fwd" else 64 if (rev or op == "coupling_bwd") else 16
+        nn = n if op == "coupling_ai_fwd" else 0
+        gx, gy = min(cdiv(items, 256), cap), B
+        ex = dict(items=items, uncapped=cdiv(items, 256))
+    else:
+        raise KeyError(op)
+    return (4 if v4 else 1, nn, gx, gy, nb, launches, g2), ex
+
+
+@functools.lru_cache(maxsize=1)
+def _planner():
+    import ctypes
+
+    from glow_tts_train import _hip
+
+    lib = _hip.load()
+    out = _hip.FlowPlan()
+    ref, fn = ctypes.byref(out), lib.glowtts_flow_plan_for
+    codes = {op: _hip.CONSTANTS["GLOWTTS_FLOW_" + c] for op, c in PLAN_OPS.items()}
+    assert sorted(codes.values()) == list(range(1, 12)) and [f for f, _ in _hip.FlowPlan._fields_] == list(PLAN_FIELDS)
+
+    def ask(op, B, C, T, n, rev, aligned):
+        """The library's plan as a tuple in the order of PLAN_FIELDS, or None where it refuses (with its error set)."""
+        if fn(codes[op], B, C, T, n, rev, aligned, ref) != 0:
+            assert lib.glowtts_last_error().decode().startswith("glowtts_flow_plan_for: ")
+            return None
+        return (out.width, out.n, out.grid_x, out.grid_y, out.nb, out.launches, out.grid2_x)
+
+    return ask
+
+
+PLAN_ROWS = SLAB + IC_BWD + IC_GEN + FUSED_BWD + CPL_FWD + CPL_BWD + CA_FWD
+
+
+def test_plans_of_the_rows():
+    """glowtts_flow_plan_for (no device is touched) for every own-shape row: the plan fields the row claims, and the figures its
+    prose names (items, the grid before its cap, the size of the last slab), which are computed from the launch rules as they
+    stood in the launchers.  A cap or a slab rule that moves fails here, on the row that no longer covers its branch."""
+    ask = _planner()
+    asked = 0
+    for (B, C, T), n, why, claims in PLAN_ROWS:
+        assert claims, why
+        for key, claim in claims.items():
+            op, rev = key.partition(":")[0], int(key.endswith(":rev"))
+            got = ask(op, B, C, T, n, rev, 1)
+            want, extras = _parent_rules(op, B, C, T, n, rev, 1)
+            assert got is not None, (key, (B, C, T), n)
+            named = {**dict(zip(PLAN_FIELDS, got)), **extras}
+            for field, value in claim.items():
+                assert named[field] == value, (key, (B, C, T), n, field, named[field], value, why)
+            assert got == want, (key, (B, C, T), n, got, want)
+            if "uncapped" in claim:
+                assert claim["uncapped"] == claim["grid_x"] + 1, "a capped row sits right behind its cap"
+            asked += 1
+    assert asked == 2 * 2 + 1 + 2 + 6 * 2 + 2 + 1 + 1
+
+
+def test_plans_of_the_shapes_every_kernel_gets():
+    """Every ALL shape, for every operation and group size it is run with: the library's plan is the launchers' former decision;
+    (2, x, 7) plans the scalar kernels, (3, x, 36) the vector kernels, and the scalar ones once a tensor is off a 16-byte boundary
+    (aligned = 0); 2 / 4 / 8 plan the register kernels, 6 and 32 the run-time-N ones; one launch but for their backward."""
+    ask = _planner()
+    for op in PLAN_OPS:
+        ns = (2, 4, 8, 6, 32) if op in _IC_OPS else (2, 4) if op in _FUSED_OPS else (0,)
+        for n in ns:
+            for param in _all_shapes(n):
+                (B, C, T), _n = param.values
+                for rev in ((0, 1) if op in ("actnorm_fwd", "coupling_fwd") else (0,)):
+                    for aligned in (1, 0):
+                        got = ask(op, B, C, T, n, rev, aligned)
+                        assert got == _parent_rules(op, B, C, T, n, rev, aligned)[0], (op, (B, C, T), n, rev, aligned, got)
+                        plan = dict(zip(PLAN_FIELDS, got))
+                        assert plan["width"] == (4 if aligned and T % 4 == 0 else 1)
+                        if T == 36:
+                            assert plan["width"] == (4 if aligned else 1), "(3, 8, 36): vector kernels, scalar once misaligned"
+                        if T == 7:
+                            assert plan["width"] == 1
+                        assert plan["n"] == (n if n in (2, 4, 8) else 0)
+                        assert plan["launches"] == (2 if op == "invconv_bwd" and n in (6, 32) else 1)
+                        assert plan["grid2_x"] == (n * n if plan["launches"] == 2 else 0)
+                        assert plan["grid_x"] >= 1 and plan["grid_y"] >= 1
+
+
+SWEEP_T = sorted(set(range(1, 41)) | {T for (_B, _C, T), _n, _why, _claims in PLAN_ROWS})
+SWEEP_B = list(range(1, 71)) + [300]
+
+
+def test_no_launch_decision_moved():
+    """The library's plan against _parent_rules for every operation, n_split in 0, 2, 4, 6, 8, 32, both directions and both
+    alignment verdicts over B in 1..70 and 300, C = the multiples of n_split (of 2 without groups) up to 400 and 2100, T in 1..40
+    and the rows' lengths.  The full product is 10^8 questions, so it is walked along its axes: every (B, T) pair at five channel
+    counts (the smallest two, G = 100 or C near 200, the largest up to 400 — ceil(200 / G) changes for the last time at G = 100
+    and 200 — and 2100), and every channel count at ten (B, T) pairs with the rows' among them.  Rejections (n_split the
+    operation does not take, C no multiple of it, odd C for the coupling) are compared at a few shapes."""
+    ask = _planner()
+    asked = 0
+    for op in PLAN_OPS:
+        grouped = op in _IC_OPS + _FUSED_OPS
+        revs = (0, 1) if op in ("actnorm_fwd", "coupling_fwd") else (0,)
+        for n in (0, 2, 4, 6, 8, 32):
+            takes_n = _parent_rules(op, 1, 64, 1, n, 0, 1) is not None
+            for C in (63, 64, 66):                            # rejections: agree on a few shapes, whatever n_split is
+                for rev in (0, 1):
+                    want = _parent_rules(op, 2, C, 8, n, rev, 1)
+                    assert ask(op, 2, C, 8, n, rev, 1) == (None if want is None else want[0]), (op, C, n)
+            assert ask(op, -1, 64, 8, n, 0, 1) is None and ask(op, 2, 0, 8, n, 0, 1) is None and ask(op, 2, 64, -1, n, 0, 1) is None
+            if not takes_n or (not grouped and n not in (0, 6)):     # n_split is not read without groups: 0 and one other value
+                continue
+            step = n if grouped else 2
+            all_c = list(range(step, 401, step)) + [2100 if 2100 % step == 0 else 2100 - 2100 % step]
+            some_c = sorted({step, 2 * step, 100 * step if 100 * step <= 400 else 200 - 200 % step, all_c[-2], all_c[-1]})
+            some_bt = [(1, 1), (2, 7), (3, 36), (5, 12), (3, 101), (70, 5), (2, 1001), (3, 1204), (2, 4099), (300, 8)]
+            for rev in revs:
+                for aligned in (1, 0):
+                    for C in some_c:
+                        for B in SWEEP_B:
+                            for T in SWEEP_T:
+                                if ask(op, B, C, T, n, rev, aligned) != _parent_rules(op, B, C, T, n, rev, aligned)[0]:
+                                    raise AssertionError((op, (B, C, T), n, rev, aligned, ask(op, B, C, T, n, rev, aligned),
+                                                          _parent_rules(op, B, C, T, n, rev, aligned)[0]))
+                        asked += len(SWEEP_B) * len(SWEEP_T)
+                    for C in all_c:
+                        for B, T in some_bt:
+                            assert ask(op, B, C, T, n, rev, aligned) == _parent_rules(op, B, C, T, n, rev, aligned)[0], (op, (B, C, T), n, rev, aligned)
+                        asked += len(some_bt)
+    print(f"{asked} plans compared")
+    assert asked > 9 * 10 ** 5
+
+
+def test_plan_for_rejects_and_empties():
+    """The argument errors of the entry points come back as an error code with glowtts_last_error set; an empty tensor plans
+    nothing (all fields 0), as the entry points launch nothing for it."""
+    import ctypes
+
+    from glow_tts_train import _hip
+
+    ask, lib = _planner(), _hip.load()
+    for op, n, shape, match in (("actnorm_invconv_fwd", 8, (2, 8, 7), "n_split=8"), ("coupling_ai_bwd", 8, (2, 8, 7), "n_split=8"),
+                                ("invconv_fwd", 34, (2, 68, 7), "n_split=34"), ("invconv_bwd", 3, (2, 9, 7), "n_split=3"),
+                                ("invconv_fwd", 4, (2, 10, 7), "not divisible"), ("coupling_ai_fwd", 4, (2, 10, 7), "bad shape"),
+                                ("coupling_fwd", 0, (2, 7, 7), "bad shape"), ("actnorm_bwd", 0, (2, 0, 7), "bad shape")):
+        assert ask(op, *shape, n, 0, 1) is None and re.search(match, lib.glowtts_last_error().decode()), (op, n, shape)
+    out = _hip.FlowPlan()
+    assert lib.glowtts_flow_plan_for(12, 2, 8, 7, 4, 0, 1, ctypes.byref(out)) != 0 and lib.glowtts_flow_plan_for(0, 2, 8, 7, 4, 0, 1, ctypes.byref(out)) != 0
+    assert lib.glowtts_flow_plan_for(1, 2, 8, 7, 4, 0, 1, None) != 0
+    for op in PLAN_OPS:
+        n = 2 if op in _IC_OPS + _FUSED_OPS else 0
+        for shape in ((0, 8, 7), (2, 8, 0)):
+            assert ask(op, *shape, n, 0, 1) == (0,) * 7, (op, shape)

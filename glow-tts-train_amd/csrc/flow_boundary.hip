@@ -37,13 +37,16 @@ __device__ __forceinline__ int bnd_channel(int k, int g, int C) { return (k / (N
 constexpr int kBndKP = 20, kBndMaxG = 12, kBndRT = 3;
 
 // D[rows of this wave's tiles][32 frames] = W X: X k-packed in LDS ([g][32][kBndKP]), W packed [g][M][16] in global memory.
-// wave w owns row tiles w, w + 4, w + 8 (rows beyond M: zero weights through the buffer descriptor's range check)
+// wave w owns row tiles w, w + 4, w + 8 (rows beyond M: zero weights through the buffer descriptor's range check; the ring's
+// look-ahead group g >= G gets a descriptor of zero bytes — the scalar offset takes no part in the range check: with it alone
+// the look-ahead read one group's image, M * 64 bytes, beyond the end of the packed weights)
 // the weights of k group `g` for this lane's row tiles (issued early by the caller for g = 0: they fly under the phase before)
 __device__ __forceinline__ void bnd_wload(const float *__restrict__ wp, int M, int G, int g, int wave, int lrow, int lk,
                                           f32x4 (&a)[kBndRT]) {
     const int wbytes = G * M * 64;
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(wp), 0, wbytes, 0x00020000);
-    const int so = g < G ? g * M * 64 : wbytes;
+    const bool g_ok = g < G;
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(wp), 0, g_ok ? wbytes : 0, 0x00020000);
+    const int so = g_ok ? g * M * 64 : 0;
 #pragma unroll
     for (int r = 0; r < kBndRT; ++r) {
         const int row = (wave + 4 * r) * 16 + lrow;

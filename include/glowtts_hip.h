@@ -258,8 +258,11 @@ int glowtts_invconv_prepare_multi(const long long *w_table, float *w_inv, long o
  * skip (B, H, T): block k's WN output; wp_end / wp_start: the convolutions' packed fp32 weights ([G][M][16], as glowtts_pack_weight*
  * writes them); logs, bias, w, logdet_w: block k + 1's ActNorm / InvConvNear (logdet_w from glowtts_invconv_prepare*).
  * Written: out (B, C, T), y (B, C, T), h0 (B, H, T), logdet (B); logdet_prev (B) is accumulated.  z is never written.
+ * skip and y_prev are read as they are, also beyond an utterance's end: out is NOT masked there (it is the end conv of whatever
+ * skip holds), y and h0 are exactly 0, and logdet_prev takes nothing from there.
  * The matrix products are convgemm_wd_kernel's (fp32 MFMA, same order): results equal those of the three launches it replaces.
- * Limits: C <= 192, H <= 192, T % 4 == 0, n_split 2 or 4, 16-byte aligned tensors (anything else: argument error). */
+ * Limits: C <= 192 and even, C / n_split <= 64, H <= 192, T % 4 == 0, n_split 2 or 4, 16-byte aligned skip, y_prev, out, y, h0 and
+ * packed weights (anything else: argument error before any launch).  B == 0 or T == 0: nothing is launched. */
 int glowtts_flow_boundary_fwd(const float *skip, const float *wp_end, const float *b_end, const float *y_prev, const float *mask,
                               const float *logs, const float *bias, const float *w, const float *logdet_w, const float *x_len,
                               const float *wp_start, const float *b_start, float *out, float *y, float *h0, float *logdet_prev,
@@ -273,7 +276,10 @@ int glowtts_flow_boundary_fwd(const float *skip, const float *wp_end, const floa
  * The ActNorm / InvConv parameter gradients leave as per-workgroup partials in `partial`
  * (B * ceil(T / 32) * (C / n_split) * (2 n_split + n_split^2) floats); glowtts_flow_boundary_bwd_reduce ADDS their sums (and the log-determinant
  * terms, as glowtts_actnorm_invconv_bwd does) into dlogs (C), dbias (C), dw (n, n) — any stream that waits for the first launch.
- * Limits as glowtts_flow_boundary_fwd. */
+ * dlogdet may be NULL in both: the first launch then takes the gradient of logdet_prev as 0, the second adds the partials' sums
+ * alone (w_inv and x_len are needed only with dlogdet).  dx_wn, dy_next, y_prev and out_prev are read as they are beyond an
+ * utterance's end; dy_prev, dout_prev and dskip are exactly 0 there (dskip with or without mask_dskip: dout_prev is 0 there).
+ * Limits as glowtts_flow_boundary_fwd; the mask is read in 16-byte pieces here and must be 16-byte aligned as well. */
 int glowtts_flow_boundary_bwd(const float *dx_wn, const float *wb_start, const float *dy_next, const float *y_prev, const float *out_prev,
                               const float *mask, const float *logs, const float *bias, const float *w, const float *dlogdet,
                               const float *wb_end, float *dy_prev, float *dout_prev, float *dskip, float *partial, int B, int C, int H,
@@ -576,7 +582,10 @@ int glowtts_flow_block_bwd(const glowtts_flow_block *blk, const float *x, const 
  *   (reference attentions.py:373-381, layers.py:73-80).
  * chan_layernorm_{fwd,bwd}_ex : the value normalised is x * mask_x[b, t] + res * keep * drop_scale (mask_x, drop may be NULL):
  *   the `x * x_mask` that opens a transformer layer and the dropout on the branch that is added back (attentions.py:64-72)
- *   never reach HBM; bwd: dx = dv * mask_x and, if dres != NULL, dres = dv * keep * drop_scale.
+ *   never reach HBM; bwd: dx = dv * mask_x and, if dres != NULL, dres = dv * keep * drop_scale (drop needs res, and in the
+ *   backward dres).  x and res are read as they are beyond an utterance's end: where mask_x is 0 and there is no residual the
+ *   column normalised is 0, so y = beta there (through the output ReLU / dropout of the `_act` forms) and dx = 0.
+ *   stats may be NULL in every forward form; C <= 768.
  * encoder_layer_{fwd,bwd} (csrc/wn_stack.hip): one post-LN transformer layer of attentions.Encoder (attentions.py:63-73 with
  *   MultiHeadAttention :204-264 and FFN :373-381) as ONE host call each way.  `L` is a HOST struct of DEVICE pointers (packed
  *   weights as for conv_fwd: q, k, v, o are 1x1, the FFN convs `taps` wide with 'same' padding, F = filter channels).
@@ -610,7 +619,9 @@ int glowtts_chan_layernorm_bwd_act(const float *x, const float *res, const float
                                    float *dgamma, float *dbeta, int B, int C, int T, glowtts_stream_t stream);
 /* Phoneme embedding (reference models.py:90,121: self.emb(x) * sqrt(hidden), transposed to (B, H, T)) and its backward:
  * out[b][h][t] = weight[ids[b][t]][h] * scale;  dweight[v][h] += scale * sum over the positions holding id v of dout[b][h][t]
- * (ids int64 (B, T); one workgroup per vocabulary entry, no atomics, no sort). */
+ * (ids int64 (B, T); one workgroup per vocabulary entry, no atomics, no sort; backward: H <= 1024).
+ * An id outside [0, V) gives a column of NaN in the forward and contributes to no row in the backward.  An element of dweight whose
+ * sum is 0 is not written: a vocabulary row that no id names keeps its value bit for bit. */
 /* Dropout keep-masks for many tensors from one launch: out[i] = 1 with probability 1 - p_drop (else 0), i < n; Philox4x32-7 keyed
  * by `seed`, counter = byte group index, so a (seed, n) pair always gives the same mask.  Stands in for the generator behind
  * F.dropout (layers.py:147, attentions.py:248): the kernels that apply dropout take such byte masks.  `out` 8-byte aligned. */

@@ -167,3 +167,88 @@ class MaskInject:
 
     def __exit__(self, *exc):
         self.ops.keep_mask_inject = None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# raw C-ABI launches with guarded buffers (tests/test_boundary_kernels.py, tests/test_encoder_kernels.py)
+U = 2.0 ** -24                                           # unit round-off of fp32
+GUARD = {torch.float32: -1234.5, torch.uint8: 165, torch.int64: -7777777}
+INT_OF = {torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64}
+PAD_BYTES = 32                                           # guard on each side: the payload stays 16-byte aligned
+
+
+def bits_equal(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.contiguous().view(INT_OF[a.dtype]), b.contiguous().view(INT_OF[b.dtype]))
+
+
+def units(got, want, scale):
+    """max over elements of |got - want| / (u * scale); where the scale is 0 the values must agree exactly."""
+    got, want, scale = got.detach().cpu().double().reshape(-1), want.detach().double().reshape(-1), scale.detach().double().reshape(-1)
+    assert got.shape == want.shape == scale.shape, (got.shape, want.shape, scale.shape)
+    err = (got - want).abs()
+    zero = scale == 0
+    assert bool((err[zero] == 0).all()), "difference where the operands are all zero"
+    if bool(zero.all()):
+        return 0.0
+    return float((err[~zero] / (U * scale[~zero])).max())
+
+
+class Dev:
+    """The buffers of one raw-ABI call, as _Dev of tests/test_flow_kernels.py: inputs are copies inside guarded buffers and must be
+    bit-identical afterwards; outputs live between guard sentinels that must survive and are pre-filled with the sentinel, or,
+    for an output that the header says is accumulated, with `init`.  `mis` names the one tensor that starts one float (4 bytes) off
+    a 16-byte boundary."""
+
+    def __init__(self, mis=None):
+        self.mis, self.ins, self.outs, self.seen = mis, [], [], set()
+
+    def _place(self, name, numel, dtype):
+        esz = torch.empty(0, dtype=dtype).element_size()
+        pad, off = PAD_BYTES // esz, (4 // esz if name == self.mis else 0)
+        self.seen.add(name)
+        buf = torch.full((numel + 2 * pad,), GUARD[dtype], dtype=dtype, device="cuda")
+        view = buf[pad + off: pad + off + numel]
+        assert buf.data_ptr() % 16 == 0 and view.data_ptr() % 16 == esz * off
+        return buf, view, pad + off
+
+    def inp(self, name, t):
+        if t is None:
+            return None
+        buf, view, lo = self._place(name, t.numel(), t.dtype)
+        view.copy_(t.reshape(-1))
+        self.ins.append((name, t, buf, lo))
+        return view.data_ptr()
+
+    def out(self, name, shape, dtype=torch.float32, init=None):
+        numel = 1
+        for s in shape:
+            numel *= int(s)
+        buf, view, lo = self._place(name, numel, dtype)
+        if init is not None:
+            assert init.numel() == numel and init.dtype == dtype
+            view.copy_(init.reshape(-1))
+        self.outs.append((name, tuple(shape), buf, lo, numel))
+        return view.data_ptr()
+
+    def finish(self):
+        torch.cuda.synchronize()
+        assert self.mis is None or self.mis in self.seen, self.mis
+        for name, t, buf, lo in self.ins:
+            b, hi = buf.cpu(), lo + t.numel()
+            assert bits_equal(b[lo:hi], t.reshape(-1)), f"input {name} changed"
+            assert bool((b[:lo] == GUARD[t.dtype]).all()) and bool((b[hi:] == GUARD[t.dtype]).all()), f"written around input {name}"
+        res = {}
+        for name, shape, buf, lo, numel in self.outs:
+            b, hi = buf.cpu(), lo + numel
+            assert bool((b[:lo] == GUARD[b.dtype]).all()) and bool((b[hi:] == GUARD[b.dtype]).all()), f"guard of output {name} overwritten"
+            res[name] = b[lo:hi].reshape(shape).clone()
+        return res
+
+
+def pack_weight(w):
+    """(M, K) -> the packed layout [G][M][16] of include/glowtts_hip.h: wp[g][m][k] = w[m][16 g + k], zeros in the slots beyond K."""
+    M, K = w.shape
+    G = (K + 15) // 16
+    wp = torch.zeros(M, G * 16, dtype=w.dtype)
+    wp[:, :K] = w
+    return wp.reshape(M, G, 16).permute(1, 0, 2).contiguous()

@@ -172,8 +172,8 @@ class MaskInject:
 # ---------------------------------------------------------------------------------------------------------------------
 # raw C-ABI launches with guarded buffers (tests/test_boundary_kernels.py, tests/test_encoder_kernels.py)
 U = 2.0 ** -24                                           # unit round-off of fp32
-GUARD = {torch.float32: -1234.5, torch.uint8: 165, torch.int64: -7777777}
-INT_OF = {torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64}
+GUARD = {torch.float32: -1234.5, torch.uint8: 165, torch.int64: -7777777, torch.int16: 0x5A3C}      # (int16: bf16 plane buffers)
+INT_OF = {torch.float32: torch.int32, torch.uint8: torch.uint8, torch.int64: torch.int64, torch.int16: torch.int16}
 PAD_BYTES = 32                                           # guard on each side: the payload stays 16-byte aligned
 
 

@@ -8,6 +8,7 @@
 // weights as a small host-side table, and gets every launch queued from C.  Weight-gradient kernels (and the final
 // un-packing) go to a second stream behind events, exactly as convops._WgradStream did.
 #include "common.hpp"
+#include "wn_plan.hpp"
 
 namespace glowtts {
 
@@ -125,131 +126,112 @@ extern "C" int glowtts_wn_fwd(const glowtts_wn_layer *layers, int n_layers, cons
                              stream);
 }
 
-extern "C" int glowtts_wn_bwd_io(const glowtts_wn_layer *layers, int n_layers, const void *x, const void *xs,
-                                 const void *acts, const void *ts, const float *mask, const unsigned char *drop,
-                                 float drop_scale, const void *dskip, void *d_rs, void *d_xin, void *dx, float *dcond,
-                                 const long long *unpack_desc, const int *unpack_prefix, int n_conv, int total_rows, int B,
-                                 int H, int T, int taps, int dil_rate, int two_source, int mask_input_grad, int io,
-                                 glowtts_stream_t wgrad_stream, glowtts_stream_t stream) {
+// The shape and form checks of a WN backward, shared with glowtts_wn_bwd_plan_for.  two_source: as the entry point `who` takes it.
+static int wn_bwd_check(const char *who, int n_layers, int B, int H, int T, int taps, int dil_rate, int io, int two_source,
+                        bool in_block) {
+    GLOWTTS_CHECK_ARG(n_layers >= 1 && B >= 0 && H > 0 && T >= 0 && taps >= 1 && (taps & 1) && dil_rate >= 1, "%s: bad shape", who);
+    GLOWTTS_CHECK_ARG(!io || !two_source, "%s: bf16 tensors use the d_rs form", who);
+    GLOWTTS_CHECK_ARG(!(in_block ? two_source != 0 : (two_source & 1)) || wn_two_source_shape(io, dil_rate, H, T),
+                      "%s: two-source form needs dilation 1, H %% 192 == 0, T %% 4 == 0", who);
+    return 0;
+}
+
+extern "C" int glowtts_wn_bwd_plan_for(int n_layers, int B, int H, int T, int taps, int dil_rate, int io, int two_source,
+                                       int in_block, glowtts_wn_bwd_plan *out) {
+    GLOWTTS_CHECK_ARG(out != nullptr, "glowtts_wn_bwd_plan_for: null pointer");
+    WN_TRY(wn_bwd_check("glowtts_wn_bwd_plan_for", n_layers, B, H, T, taps, dil_rate, io, two_source, in_block != 0));
+    *out = plan_wn_bwd(n_layers, B, H, T, dil_rate, io, two_source, in_block != 0, knob(K_WRW_BATCH) != 0);
+    return 0;
+}
+
+// The arguments of glowtts_wn_bwd_io (its comment in the header), with the plan in place of two_source.
+static int wn_bwd_impl(const glowtts_wn_layer *layers, int n_layers, const void *x, const void *xs, const void *acts, const void *ts,
+                       const float *mask, const unsigned char *drop, float drop_scale, const void *dskip, void *d_rs, void *d_xin,
+                       void *dx, float *dcond, const long long *unpack_desc, const int *unpack_prefix, int n_conv, int total_rows,
+                       int B, int H, int T, int taps, int dil_rate, int mask_input_grad, int io, glowtts_stream_t wgrad_stream,
+                       glowtts_stream_t stream, const WnBwdPlan &pl) {
     GLOWTTS_CHECK_ARG(layers && x && acts && ts && mask && dskip && d_rs && d_xin && dx, "glowtts_wn_bwd: null pointer");
-    GLOWTTS_CHECK_ARG(n_layers >= 1 && (n_layers == 1 || xs), "glowtts_wn_bwd: bad layer count / missing xs");
-    GLOWTTS_CHECK_ARG(B >= 0 && H > 0 && T >= 0 && taps >= 1 && (taps & 1) && dil_rate >= 1, "glowtts_wn_bwd: bad shape");
-    GLOWTTS_CHECK_ARG(!io || (!two_source && mask_input_grad), "glowtts_wn_bwd: bf16 tensors use the d_rs form with a masked input gradient");
+    GLOWTTS_CHECK_ARG(n_layers == 1 || xs, "glowtts_wn_bwd: missing xs");
     hipStream_t ms = (hipStream_t)stream;
     hipStream_t ws = wgrad_stream ? (hipStream_t)wgrad_stream : ms;
-    const long BHT = (long)B * H * T;
-    long dil = 1;
-    for (int i = 1; i < n_layers; ++i) dil *= dil_rate;
-    const void *dsk = dskip;
+    glowtts_stream_t wss = (glowtts_stream_t)ws;
+    const long BHT = (long)B * H * T, HT = (long)H * T;
     WN_TRY(order_after(ms, ws));                                    // accumulators were cleared on the main stream
-    // two_source bit 1 (set by glowtts_flow_block_bwd): `dskip` arrives MASKED already — the end conv's backward-data epilogue
-    // multiplied it by the mask — so the last layer's d_rs = dskip mask IS dskip and its res_skip_bwd launch (a 20 MB pass on the
-    // backward's chain, 12 per step) is not queued
-    const bool pre_masked = (two_source & 2) != 0;
-    // bit 2 (with bits 0 and 1): the caller queues the stack's 1x1 weight gradients itself (glowtts_flow_block_bwd: one
-    // glowtts_conv_wrw1_multi launch for them and the start / end convs')
-    const bool skip_wrw1 = (two_source & 4) != 0 && pre_masked;
-    two_source &= 1;
-    if (two_source) {
+    if (pl.two_source) {
         // The launch sequence of convops.WNFn._backward_layers in its two-source form, layer by layer: d_rs = [dx_{i+1} mask ;
-        // dskip] is never written (gate_bwd and wrw2 read its halves from the two tensors), each weight-gradient kernel goes to
-        // the second stream as soon as its operands exist, and only d_xin / dx live per layer.  d_rs needs B*H*T floats (the
-        // last layer's masked dskip).  fp32 tensors only.
-        GLOWTTS_CHECK_ARG(dil_rate == 1 && H % 192 == 0 && T % 4 == 0, "glowtts_wn_bwd: two-source form needs dilation 1, H %% 192 == 0, T %% 4 == 0");
+        // dskip] is never written (gate_bwd and wrw2 read its halves from the two tensors) and only d_xin / dx live per layer.
+        // d_rs needs B*H*T floats (the last layer's masked dskip).  fp32 tensors only.
         const int pad = (taps - 1) / 2;
         const float *xf = static_cast<const float *>(x), *xsf = static_cast<const float *>(xs);
         const float *actsf = static_cast<const float *>(acts), *tsf = static_cast<const float *>(ts);
         float *d_rsf = static_cast<float *>(d_rs), *d_xinf = static_cast<float *>(d_xin), *dxf = static_cast<float *>(dx);
         const float *dskf = static_cast<const float *>(dskip);
-        // Default: the dx chain of the whole stack first, then the stack's weight gradients as batched launches
-        // (glowtts_conv_wrw_batch: the 5-tap ones of all layers in one launch, the 1x1 two-source ones of layers 0 .. n-2 in
+        // Default (GLOWTTS_WN_WRW_BATCHED): the dx chain of the whole stack first, then the stack's weight gradients as batched
+        // launches (glowtts_conv_wrw_batch: the 5-tap ones of all layers in one launch, the 1x1 two-source ones of layers 0 .. n-2 in
         // another): a launch per problem ends with its split-K atomics draining before the stream's next kernel may start; in one
         // launch the next problem's workgroups take the compute units as they free up — 15.54 -> 15.30 ms per step (three
-        // alternating runs).  GLOWTTS_WRW_BATCH=0: a launch per layer, each as soon as its operands exist.
-        const bool batch = knob(K_WRW_BATCH) != 0;
-        if (batch && n_layers <= 8) {
-            const float *bx5[8], *bd5[8], *bx1[8], *bd1[8], *bd1b[8];
-            float *bw5[8], *bb5[8], *bw1[8], *bb1[8];
-            for (int i = n_layers - 1; i >= 0; --i) {
-                const glowtts_wn_layer &L = layers[i];
-                const bool last = i == n_layers - 1;
-                const float *ts_i = tsf + (long)i * 2 * BHT;
-                const unsigned char *drop_i = drop ? drop + (long)i * 2 * BHT : nullptr;
-                float *dxin_i = d_xinf + (long)i * 2 * BHT, *dx_i = dxf + (long)i * BHT;
-                const float *half = last ? nullptr : dxf + (long)(i + 1) * BHT;
-                if (last) {
-                    if (!pre_masked) {
-                        WN_TRY(glowtts_res_skip_bwd(nullptr, dskf, mask, nullptr, d_rsf, B, H, T, 1, stream));
-                        dskf = d_rsf;
-                    }
-                    WN_TRY(glowtts_conv_gate_bwd_io(dskf, nullptr, L.wb_rs, ts_i, drop_i, drop_scale, dxin_i,
-                                                    dcond ? dcond + (long)i * B * 2 * H : nullptr, B, H, H, T, 0, stream));
-                } else {
-                    WN_TRY(glowtts_conv_gate_bwd_io(half, dskf, L.wb_rs, ts_i, drop_i, drop_scale, dxin_i,
-                                                    dcond ? dcond + (long)i * B * 2 * H : nullptr, B, 2 * H, H, T, 0, stream));
-                }
-                const bool m_out = i > 0 || mask_input_grad;
-                WN_TRY(glowtts_conv_fwd(dxin_i, (long)2 * H * T, L.wb_in, nullptr, m_out ? mask : nullptr, half, (long)H * T, dx_i,
-                                        (long)H * T, B, 2 * H, H, T, taps, 1, (taps - 1) - pad, 0, m_out ? 1 : 0, 0, stream));
-                bx5[i] = i == 0 ? xf : xsf + (long)(i - 1) * BHT; bd5[i] = dxin_i; bw5[i] = L.dwp_in; bb5[i] = L.db_in;
-                bx1[i] = actsf + (long)i * BHT; bd1[i] = half; bd1b[i] = dskf; bw1[i] = L.dwp_rs; bb1[i] = L.db_rs;
+        // alternating runs).  GLOWTTS_WRW_BATCH=0, or more layers than the tables hold (_PER_LAYER): a launch per problem, each
+        // as soon as its operands exist.
+        const bool batched = pl.wrw_order == GLOWTTS_WN_WRW_BATCHED;
+        struct { const float *x[kWnTableMax], *d[kWnTableMax], *d2[kWnTableMax]; float *w[kWnTableMax], *b[kWnTableMax]; } t1, t5;
+        // a layer's weight-gradient problem of its 1x1 res/skip conv (d = [d_a ; d_b], d_a NULL in the last layer: d = d_b) or,
+        // in_conv, of its k-tap in-conv (d = d_a)
+        auto wrw = [&](int i, bool in_conv, const float *x_op, const float *d_a, const float *d_b) -> int {
+            const glowtts_wn_layer &L = layers[i];
+            if (!in_conv && pl.block_wrw1) return 0;                // in glowtts_flow_block_bwd's one launch of 1x1 problems
+            if (batched) {
+                auto &t = in_conv ? t5 : t1;
+                t.x[i] = x_op; t.d[i] = d_a; t.d2[i] = d_b;
+                t.w[i] = in_conv ? L.dwp_in : L.dwp_rs; t.b[i] = in_conv ? L.db_in : L.db_rs;
+                return 0;
             }
             WN_TRY(order_after(ms, ws));
-            const int nl = n_layers - 1;
-            if (!skip_wrw1) {
-                WN_TRY(glowtts_conv_wrw(bx1[nl], (long)H * T, dskf, (long)H * T, nullptr, nullptr, bw1[nl], bb1[nl], B, H, H, T, 1, 1, 0,
-                                        (glowtts_stream_t)ws));
-                if (nl > 0)
-                    WN_TRY(glowtts_conv_wrw_batch(nl, bx1, (long)H * T, bd1, (long)H * T, bd1b, (long)H * T, H, nullptr, nullptr, bw1, bb1, B,
-                                                  H, 2 * H, T, 1, 1, 0, (glowtts_stream_t)ws));
-            }
-            WN_TRY(glowtts_conv_wrw_batch(n_layers, bx5, (long)H * T, bd5, (long)2 * H * T, nullptr, 0, 0, nullptr, nullptr, bw5, bb5, B, H,
-                                          2 * H, T, taps, 1, pad, (glowtts_stream_t)ws));
-            if (unpack_desc)
-                WN_TRY(glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows, (glowtts_stream_t)ws));
-            return 0;
-        }
+            if (in_conv)
+                return glowtts_conv_wrw(x_op, HT, d_a, 2 * HT, nullptr, nullptr, L.dwp_in, L.db_in, B, H, 2 * H, T, taps, 1, pad, wss);
+            if (!d_a) return glowtts_conv_wrw(x_op, HT, d_b, HT, nullptr, nullptr, L.dwp_rs, L.db_rs, B, H, H, T, 1, 1, 0, wss);
+            return glowtts_conv_wrw2(x_op, HT, d_a, HT, d_b, HT, H, L.dwp_rs, L.db_rs, B, H, 2 * H, T, 1, 1, 0, wss);
+        };
         for (int i = n_layers - 1; i >= 0; --i) {
             const glowtts_wn_layer &L = layers[i];
             const bool last = i == n_layers - 1;
-            const float *x_i = i == 0 ? xf : xsf + (long)(i - 1) * BHT;
-            const float *acts_i = actsf + (long)i * BHT, *ts_i = tsf + (long)i * 2 * BHT;
-            const unsigned char *drop_i = drop ? drop + (long)i * 2 * BHT : nullptr;
-            float *dxin_i = d_xinf + (long)i * 2 * BHT, *dx_i = dxf + (long)i * BHT;
+            float *dxin_i = d_xinf + (long)i * 2 * BHT;
             const float *half = last ? nullptr : dxf + (long)(i + 1) * BHT;       // left the layer above already masked
-            if (last) {
-                if (!pre_masked) {
-                    WN_TRY(glowtts_res_skip_bwd(nullptr, dskf, mask, nullptr, d_rsf, B, H, T, 1, stream));
-                    dskf = d_rsf;
-                }
-                if (!skip_wrw1) {
-                    WN_TRY(order_after(ms, ws));
-                    WN_TRY(glowtts_conv_wrw(acts_i, (long)H * T, dskf, (long)H * T, nullptr, nullptr, L.dwp_rs, L.db_rs, B, H, H, T, 1,
-                                            1, 0, (glowtts_stream_t)ws));
-                }
-                WN_TRY(glowtts_conv_gate_bwd_io(dskf, nullptr, L.wb_rs, ts_i, drop_i, drop_scale, dxin_i,
-                                                dcond ? dcond + (long)i * B * 2 * H : nullptr, B, H, H, T, 0, stream));
-            } else {
-                if (!skip_wrw1) {
-                    WN_TRY(order_after(ms, ws));
-                    WN_TRY(glowtts_conv_wrw2(acts_i, (long)H * T, half, (long)H * T, dskf, (long)H * T, H, L.dwp_rs, L.db_rs, B, H, 2 * H,
-                                             T, 1, 1, 0, (glowtts_stream_t)ws));
-                }
-                WN_TRY(glowtts_conv_gate_bwd_io(half, dskf, L.wb_rs, ts_i, drop_i, drop_scale, dxin_i,
-                                                dcond ? dcond + (long)i * B * 2 * H : nullptr, B, 2 * H, H, T, 0, stream));
+            if (last && !pl.pre_masked) {
+                // pre_masked (glowtts_flow_block_bwd: the end conv's backward-data epilogue multiplied dskip by the mask): the last
+                // layer's d_rs = dskip mask IS dskip and this launch (a 20 MB pass on the backward's chain, 12 per step) is not queued
+                WN_TRY(glowtts_res_skip_bwd(nullptr, dskf, mask, nullptr, d_rsf, B, H, T, 1, stream));
+                dskf = d_rsf;
             }
-            WN_TRY(order_after(ms, ws));
-            WN_TRY(glowtts_conv_wrw(x_i, (long)H * T, dxin_i, (long)2 * H * T, nullptr, nullptr, L.dwp_in, L.db_in, B, H, 2 * H, T,
-                                    taps, 1, pad, (glowtts_stream_t)ws));
+            WN_TRY(wrw(i, false, actsf + (long)i * BHT, half, dskf));
+            WN_TRY(glowtts_conv_gate_bwd_io(last ? dskf : half, last ? nullptr : dskf, L.wb_rs, tsf + (long)i * 2 * BHT,
+                                            drop ? drop + (long)i * 2 * BHT : nullptr, drop_scale, dxin_i,
+                                            dcond ? dcond + (long)i * B * 2 * H : nullptr, B, last ? H : 2 * H, H, T, 0, stream));
+            WN_TRY(wrw(i, true, i == 0 ? xf : xsf + (long)(i - 1) * BHT, dxin_i, nullptr));
             // dx_i = (residual path) dx_{i+1} + (conv path) W_in^T (*) d_xin, masked unless it is the stack's own input gradient
             const bool m_out = i > 0 || mask_input_grad;
-            WN_TRY(glowtts_conv_fwd(dxin_i, (long)2 * H * T, L.wb_in, nullptr, m_out ? mask : nullptr, half, (long)H * T, dx_i,
-                                    (long)H * T, B, 2 * H, H, T, taps, 1, (taps - 1) - pad, 0, m_out ? 1 : 0, 0, stream));
+            WN_TRY(glowtts_conv_fwd(dxin_i, 2 * HT, L.wb_in, nullptr, m_out ? mask : nullptr, half, HT, dxf + (long)i * BHT, HT, B, 2 * H,
+                                    H, T, taps, 1, (taps - 1) - pad, 0, m_out ? 1 : 0, 0, stream));
         }
-        if (unpack_desc)
-            WN_TRY(glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows, (glowtts_stream_t)ws));
+        if (batched) {
+            const int nl = n_layers - 1;
+            WN_TRY(order_after(ms, ws));
+            if (!pl.block_wrw1) {
+                WN_TRY(glowtts_conv_wrw(t1.x[nl], HT, t1.d2[nl], HT, nullptr, nullptr, t1.w[nl], t1.b[nl], B, H, H, T, 1, 1, 0, wss));
+                if (nl > 0)
+                    WN_TRY(glowtts_conv_wrw_batch(nl, t1.x, HT, t1.d, HT, t1.d2, HT, H, nullptr, nullptr, t1.w, t1.b, B, H, 2 * H, T, 1, 1,
+                                                  0, wss));
+            }
+            WN_TRY(glowtts_conv_wrw_batch(n_layers, t5.x, HT, t5.d, 2 * HT, nullptr, 0, 0, nullptr, nullptr, t5.w, t5.b, B, H, 2 * H, T,
+                                          taps, 1, pad, wss));
+        }
+        if (unpack_desc) WN_TRY(glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows, wss));
         return 0;
     }
+    // The d_rs form (GLOWTTS_WN_WRW_AFTER_CHAIN): either tensor type, any dilation; d_rs (n_layers, B, 2H, T) is written.
+    const void *dsk = dskip;
+    long dil = 1;
+    for (int i = 1; i < n_layers; ++i) dil *= dil_rate;
+    const long dil_last = dil;
     for (int i = n_layers - 1; i >= 0; --i, dil /= dil_rate) {
         const glowtts_wn_layer &L = layers[i];
         const bool last = i == n_layers - 1;
@@ -266,33 +248,41 @@ extern "C" int glowtts_wn_bwd_io(const glowtts_wn_layer *layers, int n_layers, c
                                         dcond ? dcond + (long)i * B * 2 * H : nullptr, B, m_rs, H, T, io, stream));
         // dx_i = (residual path) d_rs[:H] + (conv path) W_in^T (*) d_xin ; the last layer has no residual path
         const bool m_out = i == 0 && mask_input_grad;
-        WN_TRY(glowtts_conv_fwd_io(dxin_i, (long)2 * H * T, L.wb_in, nullptr, m_out ? mask : nullptr, last ? nullptr : drs_i,
-                                   last ? 0 : (long)2 * H * T, dx_i, (long)H * T, B, 2 * H, H, T, taps, (int)dil,
-                                   (int)((taps - 1) * dil - pad), 0, m_out ? 1 : 0, 0, io, io, stream));
+        WN_TRY(glowtts_conv_fwd_io(dxin_i, 2 * HT, L.wb_in, nullptr, m_out ? mask : nullptr, last ? nullptr : drs_i, last ? 0 : 2 * HT,
+                                   dx_i, HT, B, 2 * H, H, T, taps, (int)dil, (int)((taps - 1) * dil - pad), 0, m_out ? 1 : 0, 0, io, io,
+                                   stream));
     }
     // the whole dx chain of the stack is queued first; the weight gradients follow on their own stream, where they run
     // beside the chain of whatever backward comes next (per-layer interleaving made the two streams fight for the
     // same CUs at the same time and cost 1 ms per step; a THIRD stream for the 1x1 weight gradients, beside the 5-tap ones, is
     // worth 0.05 ms per step at most — measured in round 3, not kept)
     WN_TRY(order_after(ms, ws));
-    dil = 1;
-    for (int i = 1; i < n_layers; ++i) dil *= dil_rate;
+    dil = dil_last;
     for (int i = n_layers - 1; i >= 0; --i, dil /= dil_rate) {
         const glowtts_wn_layer &L = layers[i];
-        const bool last = i == n_layers - 1;
-        const int m_rs = last ? H : 2 * H;
+        const int m_rs = i == n_layers - 1 ? H : 2 * H;
         const int pad = (int)((taps * dil - dil) / 2);
         const void *x_i = i == 0 ? x : at(xs, (long)(i - 1) * BHT, io);
-        const void *acts_i = at(acts, (long)i * BHT, io);
         const void *drs_i = at((const void *)d_rs, (long)i * 2 * BHT, io), *dxin_i = at((const void *)d_xin, (long)i * 2 * BHT, io);
-        WN_TRY(wrw_any(acts_i, (long)H * T, drs_i, (long)m_rs * T, nullptr, L.dwp_rs, L.db_rs, B, H, m_rs, T, 1, 1, 0, io,
-                       (glowtts_stream_t)ws));
-        WN_TRY(wrw_any(x_i, (long)H * T, dxin_i, (long)2 * H * T, nullptr, L.dwp_in, L.db_in, B, H, 2 * H, T, taps, (int)dil, pad, io,
-                       (glowtts_stream_t)ws));
+        WN_TRY(wrw_any(at(acts, (long)i * BHT, io), HT, drs_i, (long)m_rs * T, nullptr, L.dwp_rs, L.db_rs, B, H, m_rs, T, 1, 1, 0, io, wss));
+        WN_TRY(wrw_any(x_i, HT, dxin_i, 2 * HT, nullptr, L.dwp_in, L.db_in, B, H, 2 * H, T, taps, (int)dil, pad, io, wss));
     }
     if (unpack_desc)                                                // behind the weight-gradient kernels, on their stream
-        WN_TRY(glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows, (glowtts_stream_t)ws));
+        WN_TRY(glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows, wss));
     return 0;
+}
+
+extern "C" int glowtts_wn_bwd_io(const glowtts_wn_layer *layers, int n_layers, const void *x, const void *xs,
+                                 const void *acts, const void *ts, const float *mask, const unsigned char *drop,
+                                 float drop_scale, const void *dskip, void *d_rs, void *d_xin, void *dx, float *dcond,
+                                 const long long *unpack_desc, const int *unpack_prefix, int n_conv, int total_rows, int B,
+                                 int H, int T, int taps, int dil_rate, int two_source, int mask_input_grad, int io,
+                                 glowtts_stream_t wgrad_stream, glowtts_stream_t stream) {
+    WN_TRY(wn_bwd_check("glowtts_wn_bwd", n_layers, B, H, T, taps, dil_rate, io, two_source, false));
+    GLOWTTS_CHECK_ARG(!io || mask_input_grad, "glowtts_wn_bwd: bf16 tensors use the d_rs form with a masked input gradient");
+    return wn_bwd_impl(layers, n_layers, x, xs, acts, ts, mask, drop, drop_scale, dskip, d_rs, d_xin, dx, dcond, unpack_desc,
+                       unpack_prefix, n_conv, total_rows, B, H, T, taps, dil_rate, mask_input_grad, io, wgrad_stream, stream,
+                       plan_wn_bwd(n_layers, B, H, T, dil_rate, io, two_source, false, knob(K_WRW_BATCH) != 0));
 }
 
 extern "C" int glowtts_wn_bwd(const glowtts_wn_layer *layers, int n_layers, const float *x, const float *xs,
@@ -397,11 +387,12 @@ extern "C" int glowtts_flow_block_bwd_io(const glowtts_flow_block *blk, const vo
     const bool skip_end_bd = (io & GLOWTTS_FB_SKIP_END) != 0, skip_start_bd = (io & GLOWTTS_FB_SKIP_START) != 0;
     GLOWTTS_CHECK_ARG((!skip_end_bd || skip_cpl) && (!skip_start_bd || skip_ai), "glowtts_flow_block_bwd: io bits 11 / 12 need bits 9 / 8");
     io &= 255;
-    GLOWTTS_CHECK_ARG(!io || !two_source, "glowtts_flow_block_bwd: bf16 tensors use the d_rs form");
     GLOWTTS_CHECK_ARG(!(skip_ai || skip_cpl) || io == 0, "glowtts_flow_block_bwd: the fused-flow flags go with fp32 tensors");
     const int io_h = io & 1, io_f = (io >> 1) & 1;
     GLOWTTS_CHECK_ARG(io_h || !io_f, "glowtts_flow_block: a bf16 flow tensor needs bf16 hidden tensors (io = 0, 1 or 3)");
     GLOWTTS_CHECK_ARG(io != 1 || y0h, "glowtts_flow_block_bwd: io = 1 needs the y0h buffer");
+    WN_TRY(wn_bwd_check("glowtts_flow_block_bwd", blk->n_layers, B, H, T, taps, dil_rate, io_h, two_source, true));
+    const WnBwdPlan pl = plan_wn_bwd(blk->n_layers, B, H, T, dil_rate, io_h, two_source, true, knob(K_WRW_BATCH) != 0);
     const void *start_in = io == 1 ? y0h : y;
     const long start_bs = io == 1 ? (long)(C / 2) * T : (long)C * T;
     hipStream_t ms = (hipStream_t)stream;
@@ -418,29 +409,26 @@ extern "C" int glowtts_flow_block_bwd_io(const glowtts_flow_block *blk, const vo
     // Round 4, two-source form: the block's SIX 1x1 weight gradients (end conv, start conv, the stack's last and two-source
     // res/skip convs) are one launch behind the block's chain (glowtts_conv_wrw1_multi: 9 tiles of 192 x 192 sharing the compute
     // units) — alone they were launches of 22 us for < 1 us of matrix work each, and 88 us for the batch of three.
-    const bool multi1 = two_source && !io && blk->n_layers >= 1 && blk->n_layers + 2 <= 8 && H % 64 == 0;
-    if (!multi1) {
+    if (!pl.block_wrw1) {
         WN_TRY(order_after(ms, ws));
         WN_TRY(wrw_any(skip, HT, dout, CT, nullptr, blk->dwp_end, blk->db_end, B, H, C, T, 1, 1, 0, io_h, (glowtts_stream_t)ws));
     }
-    // (two-source form: dskip leaves this conv masked, which is the last WN layer's d_rs — see glowtts_wn_bwd_io)
-    const int pre_mask = (two_source && !io) ? 1 : 0;
+    // (two-source form: dskip leaves this conv masked, which is the last WN layer's d_rs — see wn_bwd_impl)
     if (!skip_end_bd)
-        WN_TRY(glowtts_conv_fwd_io(dout, CT, blk->wb_end, nullptr, pre_mask ? mask : nullptr, nullptr, 0, dskip, HT, B, C, H, T, 1, 1, 0, 0,
-                                   pre_mask, 0, io_h, io_h, stream));
+        WN_TRY(glowtts_conv_fwd_io(dout, CT, blk->wb_end, nullptr, pl.pre_masked ? mask : nullptr, nullptr, 0, dskip, HT, B, C, H, T, 1, 1,
+                                   0, 0, pl.pre_masked, 0, io_h, io_h, stream));
     // the gated conv stack (its weight gradients go to the second stream as well; un-packing is done below for the block).
     // With bf16 tensors the stack masks its own input gradient: the start conv's weight gradient then needs no mask.
-    WN_TRY(glowtts_wn_bwd_io(blk->layers, blk->n_layers, h0, xs, acts, ts, mask, drop, drop_scale, dskip, d_rs, d_xin, dx_wn, dcond,
-                             nullptr, nullptr, 0, 0, B, H, T, taps, dil_rate,
-                             two_source ? (1 | (pre_mask << 1) | ((multi1 && pre_mask) ? 4 : 0)) : 0, io_h, io_h, wgrad_stream, stream));
+    WN_TRY(wn_bwd_impl(blk->layers, blk->n_layers, h0, xs, acts, ts, mask, drop, drop_scale, dskip, d_rs, d_xin, dx_wn, dcond, nullptr,
+                       nullptr, 0, 0, B, H, T, taps, dil_rate, io_h, io_h, wgrad_stream, stream, pl));
     // start conv (C/2 -> H, 1x1, output masked): its input gradient is ADDED into dy[:, :C/2] where the affine apply left dz0
     WN_TRY(order_after(ms, ws));
-    if (multi1 && pre_mask) {
+    if (pl.block_wrw1) {
         const int nl = blk->n_layers;
         const long BHT = (long)B * H * T;
         const float *actsf = static_cast<const float *>(acts), *dxw = static_cast<const float *>(dx_wn);
         const float *dskf = static_cast<const float *>(dskip);                 // masked by the end conv's backward-data epilogue
-        glowtts_wrw1_problem pr[8] = {};
+        glowtts_wrw1_problem pr[kWnTableMax] = {};
         int np = 0;
         for (int i = 0; i < nl; ++i) {                                        // res/skip convs: x = acts_i, d = [dx_{i+1} mask ; dskip]
             const glowtts_wn_layer &L = blk->layers[i];

@@ -39,6 +39,7 @@ EncLayer = _STRUCTS["glowtts_enc_layer"]
 ConvPlan = _STRUCTS["glowtts_conv_plan"]          # written BY the library: glowtts_conv_plan_next
 AttnPlan = _STRUCTS["glowtts_attn_plan"]          # ... glowtts_attn_plan_for
 FlowPlan = _STRUCTS["glowtts_flow_plan"]          # ... glowtts_flow_plan_for
+WnBwdPlan = _STRUCTS["glowtts_wn_bwd_plan"]       # ... glowtts_wn_bwd_plan_for
 
 EXPORTED_SYMBOLS = sorted(_FUNCTIONS)
 

@@ -851,6 +851,26 @@ def _wn_layers_from_slabs(x, xs, acts, ts, n_layers):
     return out
 
 
+@functools.lru_cache(maxsize=256)                                      # (a training run sees few shapes: asked once per shape)
+def _wn_bwd_plan(n_layers, B, H, T, taps, dil_rate, io, in_block, want=True):
+    """(two-source form?, elements of the d_rs workspace) of a WN stack's backward as the library plans it (csrc/wn_plan.hpp,
+    glowtts_wn_bwd_plan_for): the two-source launch sequence (d_rs never materialised, batched weight gradients) wherever the
+    library's shape rule allows it and the caller's own terms (`want`) do — also where the weight gradients stay on the chain's
+    stream, the backward's last block and every block of a one-stream run (rocprofv3 passes then time the launches the step
+    really makes): 14.83 -> 14.75 ms per step (tools/ab_flags.py, four alternating pairs)."""
+    lib = _hip.load()
+
+    def ask(two_source):
+        plan = _hip.WnBwdPlan()
+        if lib.glowtts_wn_bwd_plan_for(n_layers, B, H, T, taps, dil_rate, io, two_source, int(in_block), ctypes.byref(plan)) != 0:
+            raise RuntimeError(lib.glowtts_last_error().decode())
+        return plan
+    plan = ask(0)
+    if want and plan.two_source_ok:
+        plan = ask(1)
+    return bool(plan.two_source), int(plan.d_rs_elems)
+
+
 class WNFn(Function):
     """The whole WN stack (reference layers.py:138-162) as one autograd node.
 
@@ -965,8 +985,8 @@ class WNFn(Function):
         wgrad = _WgradStream(dev)
         # virtual concat of d_rs (no res_skip_bwd launch, no d_rs tensor): needs the frame-packed wrw and whole 96-channel
         # chunks per source, gradients written in place, no conditioning input and unit dilation
-        two_src = (sink.direct and not has_cond and dil_rate == 1 and H % 192 == 0 and T % 4 == 0 and _hip.timing_off()
-                   and all(params[6 * j + 5] is not None for j in range(n_layers)))
+        two_src = (sink.direct and not has_cond and _hip.timing_off() and all(params[6 * j + 5] is not None for j in range(n_layers))
+                   and _wn_bwd_plan(n_layers, B, H, T, params[0].shape[2], dil_rate, 0, False)[0])
         for i in reversed(range(n_layers)):
             in_v, in_g, in_b, rs_v, rs_g, rs_b = params[6 * i: 6 * i + 6]
             x_i, acts, ts = saved[3 * i: 3 * i + 3]
@@ -1070,8 +1090,8 @@ class WNFn(Function):
         dskip = dout.contiguous()
         wgrad = _WgradStream(dev)
         # two-source form (the launch sequence of _backward_layers): no d_rs tensor, weight gradients interleaved per layer
-        two_src = wgrad.enabled and dil_rate == 1 and H % 192 == 0 and T % 4 == 0
-        d_rs = torch.empty((B, H, T) if two_src else (n_layers, B, 2 * H, T), device=dev, dtype=torch.float32)
+        two_src, n_rs = _wn_bwd_plan(n_layers, B, H, T, taps, dil_rate, 0, False, want=wgrad.enabled)
+        d_rs = torch.empty(n_rs, device=dev, dtype=torch.float32)
         d_xin = torch.empty(n_layers, B, 2 * H, T, device=dev, dtype=torch.float32)
         dx = torch.empty(n_layers, B, H, T, device=dev, dtype=torch.float32)
         plan.dwp.zero_()
@@ -1359,13 +1379,6 @@ def _flow_grad_inputs(dz, dlogdet, x, io):
     return dz, dlogdet
 
 
-def _two_src(io, dil_rate, H, T):
-    # the two-source launch sequence (d_rs never materialised, batched weight gradients) also where the weight gradients stay
-    # on the chain's stream — the backward's last block, and every block of a one-stream run (rocprofv3 passes then time the
-    # launches the step really makes): 14.83 -> 14.75 ms per step (tools/ab_flags.py, four alternating pairs)
-    return (not io) and dil_rate == 1 and H % 192 == 0 and T % 4 == 0
-
-
 def _record_for_wgrad(stream, *tensors):
     """`tensors` are read by launches on `stream` that may run after the node that owns them has returned — the MASKS included: the
     start conv's weight gradient multiplies its d operand by the mask (the only 1x1 weight gradient that does).  It is a small
@@ -1452,10 +1465,10 @@ class FlowBlockFn(Function):
         wgrad = _WgradStream(dev)
         if block_index < _WGRAD_MAIN_BLOCKS:
             wgrad.enabled = False                    # the backward's last blocks: their weight gradients stay on the chain's stream
-        two_src = _two_src(io, dil_rate, H, T)
+        two_src, n_rs = _wn_bwd_plan(n_layers, B, H, T, ctx.taps, dil_rate, int(io) & 1, True)
         dy, dout, dx = flow(B, C, T), new(B, C, T), flow(B, C, T)
         dskip = new(B, H, T)
-        d_rs = new(B, H, T) if two_src else new(n_layers, B, 2 * H, T)
+        d_rs = new(n_rs)
         d_xin, dx_wn = new(n_layers, B, 2 * H, T), new(n_layers, B, H, T)
         slabs = FlowSlabs(1, n_layers, B, C, H, T, io, n_split, ctx.scale,
                           [ptr(t) for t in (x, m2, x_len, drop, y, y0h, h0, xs, acts, ts, skip, out)] + [None, None, ptr(winv)],
@@ -1620,12 +1633,12 @@ class FlowStackFn(Function):
         flow = lambda *shape: torch.empty(shape, device=dev, dtype=fdt)                               # noqa: E731
         dz, dlogdet = _flow_grad_inputs(dz, dlogdet, x, io)
         wgrad = _WgradStream(dev)
-        two_src = _two_src(io, dil_rate, H, T)
+        two_src, n_rs = _wn_bwd_plan(n_layers, B, H, T, ctx.taps, dil_rate, int(io) & 1, True)
         # per-block scratch as slices of one allocation per kind: the weight-gradient stream reads a block's scratch after the
         # chain has moved on to the next block, so nothing is shared between blocks
         dy, dout, dxs = flow(nb, B, C, T), act(nb, B, C, T), flow(nb, B, C, T)
         dskip = act(nb, B, H, T)
-        d_rs = act(nb, B, H, T) if two_src else act(nb, n_layers, B, 2 * H, T)
+        d_rs = act(nb, n_rs)
         d_xin, dx_wn = act(nb, n_layers, B, 2 * H, T), act(nb, n_layers, B, H, T)
         slabs = FlowSlabs(nb, n_layers, B, C, H, T, io, n_split, ctx.scale,
                           [ptr(t) for t in (x, m2, x_len, drops, y, y0h, h0, xs, acts, ts, skip, out, zs)] + [None, ptr(winv)],

@@ -515,9 +515,14 @@ int glowtts_gate_bwd_ts(const float *ts, const float *dacts, const unsigned char
  *       bias gradients into layers[i].db_*; the weight-gradient kernels and, if unpack_desc != NULL, the final
  *       glowtts_unpack_weight_grad_multi(unpack_desc, unpack_prefix, n_conv, total_rows) run on wgrad_stream behind
  *       events (NULL: everything on `stream`).  The caller keeps every buffer alive until wgrad_stream has drained.
- *       two_source: bit 0 = the two-source launch sequence (d_rs = [dx mask ; dskip] is never materialised; fp32 tensors,
- *       dilation 1, H % 192 == 0, T % 4 == 0); bit 1 (with bit 0) = `dskip` is masked already (glowtts_flow_block_bwd masks it in
- *       the end conv's backward-data epilogue), so the last layer's dskip * mask pass is not queued. */
+ *       two_source, bit by bit (glowtts_wn_bwd_plan_for below says what a value makes of a shape):
+ *         bit 0 = the two-source launch sequence: d_rs = [dx mask ; dskip] is never materialised (the kernels that read it take its
+ *                 halves from the two tensors) and is a workspace of B*H*T elements, the last layer's masked dskip; fp32 tensors,
+ *                 dilation 1, H % 192 == 0, T % 4 == 0, else the call is rejected.  Clear: the d_rs form, bits 1 and 2 mean nothing.
+ *         bit 1 (with bit 0) = `dskip` is masked already, so the last layer's dskip * mask pass is not queued;
+ *         bit 2 (with bits 0 and 1) = the caller queues the stack's 1x1 res/skip weight gradients itself.
+ *       Higher bits are ignored.  (glowtts_flow_block_bwd's own two_source is a flag: non-zero asks for the form; the block masks
+ *       dskip in its end conv's backward-data epilogue and may send the 1x1 weight gradients in one launch with its own.) */
 typedef struct glowtts_wn_layer {
     const float *wf_in, *wb_in, *b_in;   /* packed forward / backward-data weights and bias of the k-tap in-conv */
     const float *wf_rs, *wb_rs, *b_rs;   /* ... of the 1x1 res/skip conv (2H rows, H in the last layer) */
@@ -532,6 +537,33 @@ int glowtts_wn_bwd(const glowtts_wn_layer *layers, int n_layers, const float *x,
                    float *d_rs, float *d_xin, float *dx, const long long *unpack_desc, const int *unpack_prefix,
                    int n_conv, int total_rows, int B, int H, int T, int taps, int dil_rate, int two_source,
                    glowtts_stream_t wgrad_stream, glowtts_stream_t stream);
+
+/* ---- what would this WN backward queue?  (no reference counterpart; csrc/wn_plan.hpp) -------------------------------------
+ * The decision glowtts_wn_bwd(_io) (in_block = 0; two_source as above) or glowtts_flow_block_bwd(_io) (in_block = 1; two_source its
+ * flag, io its hidden tensors' type) makes for a stack of n_layers layers — a pure host function: it touches no device and works on
+ * a machine without a GPU; the WRW_BATCH switch is read as the executor reads it.  Non-zero (and glowtts_last_error) for what
+ * that call rejects: a bad shape, bf16 tensors or a shape outside the rule with the two-source form asked for.
+ *   two_source_ok : the shape rule alone: fp32 tensors, dilation 1, H % 192 == 0, T % 4 == 0 — whatever was asked for
+ *   two_source    : the form queued: 1 = two-source, 0 = d_rs
+ *   pre_masked    : two-source form: dskip arrives masked, no res_skip_bwd launch for the last layer
+ *   block_wrw1    : two-source form: the stack queues no 1x1 weight gradient; the block sends them with the start and end
+ *                   convs' as one glowtts_conv_wrw1_multi launch (n_layers + 2 <= 8 problems, H % 64 == 0)
+ *   wrw_order     : when the weight gradients go to wgrad_stream: GLOWTTS_WN_WRW_AFTER_CHAIN (d_rs form: a launch per problem behind
+ *                   the whole dx chain), _BATCHED (two-source form, WRW_BATCH on, n_layers <= 8: batched launches behind the chain),
+ *                   _PER_LAYER (two-source form otherwise: a launch per problem as soon as its operands exist)
+ *   chain_calls, wgrad_calls : inner entry-point calls queued on `stream` / on wgrad_stream (the un-packing not counted)
+ *   d_rs_elems    : elements of the d_rs workspace: B*H*T (two-source form) or n_layers*B*2H*T */
+#define GLOWTTS_WN_WRW_AFTER_CHAIN 0
+#define GLOWTTS_WN_WRW_BATCHED 1
+#define GLOWTTS_WN_WRW_PER_LAYER 2
+typedef struct glowtts_wn_bwd_plan {
+    int32_t two_source_ok, two_source, pre_masked, block_wrw1;
+    int32_t wrw_order;
+    int32_t chain_calls, wgrad_calls;
+    int64_t d_rs_elems;
+} glowtts_wn_bwd_plan;
+int glowtts_wn_bwd_plan_for(int n_layers, int B, int H, int T, int taps, int dil_rate, int io, int two_source, int in_block,
+                            glowtts_wn_bwd_plan *out);
 
 /* ---- a whole flow block per call (csrc/wn_stack.hip): [ActNorm, InvConvNear, CouplingBlock], models.py:176-190 ---------
  * The launch sequence of one decoder block in the forward (training) direction, without conditioning input, n_split in

@@ -71,7 +71,7 @@ def test_cabi_struct_layouts_match_the_c_compiler(tmp_path):
 
     structs = {"glowtts_wn_layer": _hip.WnLayer, "glowtts_wrw1_problem": _hip.Wrw1Problem, "glowtts_flow_block": _hip.FlowBlock,
                "glowtts_enc_layer": _hip.EncLayer, "glowtts_conv_plan": _hip.ConvPlan, "glowtts_attn_plan": _hip.AttnPlan,
-               "glowtts_flow_plan": _hip.FlowPlan}
+               "glowtts_flow_plan": _hip.FlowPlan, "glowtts_wn_bwd_plan": _hip.WnBwdPlan}
     assert sorted(structs) == sorted(re.findall(r"typedef\s+struct\s+(\w+)", open(_cabi.HEADER_PATH).read()))
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "glowtts_hip.h"', 'int main(void) {']
     for name, cls in structs.items():

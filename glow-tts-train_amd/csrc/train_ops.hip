@@ -8,8 +8,10 @@
 //                                                                  gradient holds a NaN or an Inf is skipped without a host read
 //   an exponential moving average of the parameters, kept by the   (no reference counterpart) — one more stream in and out of the
 //   Adam/Noam pass, and the exchange of two flat buffers             update kernel instead of a second pass over p
-// The tail is ONE kernel per pass — clip_kernel<V, SCALE, GUARD>, adam_kernel<V, GUARD, EMA>, adam_advance_kernel — behind eight
-// entry points: an option is a compile-time flag of the pass it belongs to, so the default forms carry none of its instructions.
+//   parameter groups in the same update                            (torch.optim.Adam's per-group options) — a rate scale, L2 or
+//                                                                  decoupled weight decay, or "frozen" per contiguous range
+// The tail is ONE kernel per pass — clip_kernel<V, SCALE, GUARD>, adam_kernel<V, GUARD, EMA[, GroupTable]>, adam_advance_kernel —
+// behind nine entry points: an option is a compile-time flag of the pass it belongs to, so the default forms carry none of its instructions.
 // The flat kernels choose 16-byte or scalar access per launch through vec4_or_scalar (common.hpp).
 #include "common.hpp"
 
@@ -245,14 +247,49 @@ __device__ __forceinline__ float noam_rate(float step, float lr, float dim_model
     return (float)((double)lr * (1.0 / sqrt((double)dim_model)) * (a < b ? a : b));
 }
 
+// Parameter groups of one launch, a kernel argument BY VALUE (the entry point fills it from its host arrays: nothing of them is
+// read after the call, and a captured graph replays with the table it was captured with).  The launch covers the LIVE elements
+// only: a frozen group has no index at all, so nothing of its p, m, v, e — or g — is streamed.  Live index i (in units of the
+// access width) belongs to the first group k with i < end[k], and its element is i + shift[k]; the entries from the number of
+// groups on repeat the total, so they never match.  step / pmul / l2 are formed in the kernel, once per thread (group_rates).
+constexpr int kMaxGroups = GLOWTTS_MAX_PARAM_GROUPS;
+struct GroupTable {
+    long end[kMaxGroups];         // exclusive end of group k among the live indices, ascending
+    long shift[kMaxGroups];       // first element of group k minus its first live index
+    float lr_scale[kMaxGroups];
+    float wd[kMaxGroups];
+    unsigned decoupled;           // bit k: group k's decay is the decoupled one (AdamW), else L2
+};
+
+// What one group's elements are updated with.  dec / l2 say whether a decay is applied AT ALL: weight_decay == 0 takes the plain
+// expressions through a select (-0.0f + 0.0f * p is +0.0f, and m's bits would differ from the plain kernel's).
+struct GroupRates {
+    float step;                   // step_size of adam_update, from rate_k = fl32(lr_t * lr_scale)
+    float pmul;                   // decoupled: p *= 1 - rate_k wd first (fp64, one rounding, as torch forms the factor on the host)
+    float wd;                     // L2: g' = g + wd p goes into the moments
+    bool dec, l2;
+};
+
+__device__ __forceinline__ GroupRates group_rates(const GroupTable &tab, int k, float lr_t, double bc1) {
+    const float rate = lr_t * tab.lr_scale[k];
+    const bool decoupled = (tab.decoupled >> k) & 1u, on = tab.wd[k] != 0.f;
+    return {(float)((double)rate / bc1), (float)(1.0 - (double)rate * (double)tab.wd[k]), tab.wd[k], on && decoupled, on && !decoupled};
+}
+
 // EMA: the same pass also moves an average e of the parameters towards the NEW p, e += a (p_new - e) — the difference form: the
 // increment is formed from a small number, so fp32 holds it where d e + (1 - d) p would round 1 - d away.  With EMA = false e and
 // a are not touched, and the code is what it was before the flag existed.
-template <int V, bool EMA>
+// GROUPS (`tab` is then one GroupTable, else nothing): per-group rate scale and weight decay, frozen groups left out.  Every index
+// into the table is a compile-time one (unrolled selects over at most 8 ends), so the table stays in scalar registers: no LDS, no
+// device memory, no scratch.  With lr_scale = 1 and no decay an element is updated by the plain form's operations, bit for bit.
+template <int V, bool EMA, class... Groups>
 __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                             float *__restrict__ v, long nv, const float *__restrict__ state, float lr, float b1,
-                                            float b2, float eps, float dim_model, float warmup, float *__restrict__ e, float a) {
-    // torch.optim.Adam (no amsgrad, no weight decay): step_size = lr_t / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
+                                            float b2, float eps, float dim_model, float warmup, float *__restrict__ e, float a,
+                                            const Groups &...tab) {
+    constexpr bool GROUPS = sizeof...(Groups) == 1;
+    static_assert(sizeof...(Groups) <= 1, "at most one group table");
+    // torch.optim.Adam (no amsgrad): step_size = lr_t / (1 - b1^t); denom = sqrt(v)/sqrt(1 - b2^t) + eps
     const float t = state[0];
     // state[3] > 0: a learning rate imposed for this one update (a resumed optimizer applies the rate stored in its
     // checkpoint before its schedule takes over again, as torch's load_state_dict leaves it in the reference)
@@ -261,25 +298,54 @@ __device__ __forceinline__ void adam_update(float *__restrict__ p, const float *
     const double bc2 = 1.0 - pow((double)b2, (double)t);
     const float step_size = (float)((double)lr_t / bc1);
     const float inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    [[maybe_unused]] GroupRates rates[GROUPS ? kMaxGroups : 1];
+    if constexpr (GROUPS) {
+        const GroupTable &tb = (tab, ...);
+#pragma unroll
+        for (int k = 0; k < kMaxGroups; ++k) rates[k] = group_rates(tb, k, lr_t, bc1);
+    }
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
-        Vec<V> pv = Vec<V>::load(p + i * V);
-        Vec<V> gv = Vec<V>::load(g + i * V);
-        Vec<V> mv = Vec<V>::load(m + i * V);
-        Vec<V> vv = Vec<V>::load(v + i * V);
+        long at = i;                                  // the element (in units of V) this live index stands for
+        [[maybe_unused]] GroupRates r{};
+        if constexpr (GROUPS) {
+            const GroupTable &tb = (tab, ...);
+            r = rates[0];
+            at = i + tb.shift[0];
+#pragma unroll
+            for (int k = 1; k < kMaxGroups; ++k) {
+                const bool past = i >= tb.end[k - 1];
+                at = past ? i + tb.shift[k] : at;
+                r.step = past ? rates[k].step : r.step;
+                r.pmul = past ? rates[k].pmul : r.pmul;
+                r.wd = past ? rates[k].wd : r.wd;
+                r.dec = past ? rates[k].dec : r.dec;
+                r.l2 = past ? rates[k].l2 : r.l2;
+            }
+        }
+        Vec<V> pv = Vec<V>::load(p + at * V);
+        Vec<V> gv = Vec<V>::load(g + at * V);
+        Vec<V> mv = Vec<V>::load(m + at * V);
+        Vec<V> vv = Vec<V>::load(v + at * V);
         Vec<V> ev;
-        if constexpr (EMA) ev = Vec<V>::load(e + i * V);
+        if constexpr (EMA) ev = Vec<V>::load(e + at * V);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
+            float step = step_size;
+            if constexpr (GROUPS) {
+                step = r.step;
+                gv[j] = r.l2 ? gv[j] + r.wd * pv[j] : gv[j];
+                pv[j] = r.dec ? pv[j] * r.pmul : pv[j];
+            }
             mv[j] = b1 * mv[j] + (1.0f - b1) * gv[j];
             vv[j] = b2 * vv[j] + (1.0f - b2) * gv[j] * gv[j];
             const float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-            pv[j] -= step_size * (mv[j] / denom);
+            pv[j] -= step * (mv[j] / denom);
             if constexpr (EMA) ev[j] += a * (pv[j] - ev[j]);
         }
-        pv.store(p + i * V);
-        mv.store(m + i * V);
-        vv.store(v + i * V);
-        if constexpr (EMA) ev.store(e + i * V);
+        pv.store(p + at * V);
+        mv.store(m + at * V);
+        vv.store(v + at * V);
+        if constexpr (EMA) ev.store(e + at * V);
     }
 }
 
@@ -298,17 +364,19 @@ __device__ __forceinline__ float ema_weight(float t, float ema_rate, int ema_war
 // GUARD: the update stands behind the flag the guarded clip pass left (guard[0] != 0: a non-finite gradient element was seen) — the
 // whole grid leaves before it has read or written anything of p, m, v or e.
 // EMA: the average e is carried along (adam_update); p, m and v come out as without it.
-template <int V, bool GUARD, bool EMA>
+// Groups: nothing, or one GroupTable as the last argument (adam_update's GROUPS form; nv then counts the live indices) — the forms
+// without a table have the arguments, and the code, they had before parameter groups existed.
+template <int V, bool GUARD, bool EMA, class... Groups>
 __global__ __launch_bounds__(256) void adam_kernel(float *__restrict__ p, const float *__restrict__ g, float *__restrict__ m,
                                                    float *__restrict__ v, float *__restrict__ e, long nv,
                                                    const float *__restrict__ state, const float *__restrict__ guard, float lr,
                                                    float b1, float b2, float eps, float dim_model, float warmup, float ema_rate,
-                                                   int ema_warm, float ema_t0) {
+                                                   int ema_warm, float ema_t0, Groups... tab) {
     if constexpr (GUARD)
         if (guard[0] != 0.f) return;
     float a = 0.f;
     if constexpr (EMA) a = ema_weight(state[0], ema_rate, ema_warm, ema_t0);
-    adam_update<V, EMA>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup, e, a);
+    adam_update<V, EMA>(p, g, m, v, nv, state, lr, b1, b2, eps, dim_model, warmup, e, a, tab...);
 }
 
 // a <-> b in one pass (FlatAdam.swap_ema: the averaged weights change places with the raw ones, no pointer moves)
@@ -372,6 +440,37 @@ static void launch_adam(float *p, const float *g, float *m, float *v, float *e, 
     vec4_or_scalar(n, {p, g, m, v, e}, [&](auto V, long nv) {
         hipLaunchKernelGGL((adam_kernel<V, GUARD, EMA>), dim3(stream_grid(nv)), dim3(256), 0, s, p, g, m, v, e, nv, state, guard, lr,
                            b1, b2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0);
+    });
+}
+
+// launch_adam over parameter groups (glowtts_adam_noam_groups has checked group_end / group_opts).  The 16-byte form needs every
+// group end on a multiple of 4 besides the pointers' alignment: a group that began inside a float4 would share it with its
+// neighbour.  The grid is sized to the live elements; with every group frozen nothing is launched.
+template <bool GUARD, bool EMA>
+static void launch_adam_groups(float *p, const float *g, float *m, float *v, float *e, const int64_t *group_end,
+                               const float *group_opts, int n_groups, const float *state, const float *guard, float lr, float b1,
+                               float b2, float eps, float dim_model, float warmup, float ema_rate, int ema_warm, float ema_t0,
+                               hipStream_t s) {
+    bool wide = all_aligned16({p, g, m, v, e});
+    for (int k = 0; k < n_groups; ++k) wide = wide && (group_end[k] & 3) == 0;
+    as_bool(wide, [&](auto W) {
+        constexpr int V = decltype(W)::value ? 4 : 1;
+        GroupTable tab{};
+        long live = 0, start = 0;
+        for (int k = 0; k < kMaxGroups; ++k) {
+            const bool used = k < n_groups, frozen = used && group_opts[4 * k + 3] != 0.f;
+            const long end = used ? (long)group_end[k] / V : start;
+            tab.shift[k] = start - live;
+            if (!frozen) live += end - start;
+            tab.end[k] = live;
+            tab.lr_scale[k] = used ? group_opts[4 * k] : 1.0f;
+            tab.wd[k] = used ? group_opts[4 * k + 1] : 0.0f;
+            if (used && group_opts[4 * k + 2] != 0.f) tab.decoupled |= 1u << k;
+            start = end;
+        }
+        if (live == 0) return;
+        hipLaunchKernelGGL((adam_kernel<V, GUARD, EMA, GroupTable>), dim3(stream_grid(live)), dim3(256), 0, s, p, g, m, v, e, live,
+                           state, guard, lr, b1, b2, eps, dim_model, warmup, ema_rate, ema_warm, ema_t0, tab);
     });
 }
 
@@ -542,6 +641,40 @@ extern "C" int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *
                                                                            dim_model, warmup, ema_rate, ema_warm, ema_t0,
                                                                            (hipStream_t)stream);
     GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_ema");
+}
+
+// GUARD and EMA are both chosen here, from guard != NULL and e != NULL.  group_end / group_opts are HOST arrays: what the kernel needs
+// of them travels in its arguments (launch_adam_groups), so they may be freed or rewritten as soon as this returns.
+extern "C" int glowtts_adam_noam_groups(float *p, const float *g, float *m, float *v, float *e, int64_t n, const float *state,
+                                        const float *guard, float lr, float beta1, float beta2, float eps, float dim_model,
+                                        float warmup, float ema_rate, int ema_warm, float ema_t0, const int64_t *group_end,
+                                        const float *group_opts, int n_groups, glowtts_stream_t stream) {
+    GLOWTTS_CHECK_ARG(p && g && m && v && state && group_end && group_opts, "glowtts_adam_noam_groups: null pointer");
+    GLOWTTS_CHECK_ARG(n >= 0, "glowtts_adam_noam_groups: negative size");
+    GLOWTTS_CHECK_ARG(n_groups >= 1 && n_groups <= GLOWTTS_MAX_PARAM_GROUPS,
+                      "glowtts_adam_noam_groups: n_groups = %d, expected 1 .. %d (GLOWTTS_MAX_PARAM_GROUPS)", n_groups,
+                      GLOWTTS_MAX_PARAM_GROUPS);
+    GLOWTTS_CHECK_ARG(e == nullptr || (ema_rate > 0.f && ema_rate < 1.f),
+                      "glowtts_adam_noam_groups: ema_rate (1 - decay) must lie in (0, 1)");
+    int64_t last = 0;
+    for (int k = 0; k < n_groups; ++k) {
+        GLOWTTS_CHECK_ARG(group_end[k] >= last, "glowtts_adam_noam_groups: group ends must ascend (group %d)", k);
+        last = group_end[k];
+        const float *o = group_opts + 4 * k;
+        GLOWTTS_CHECK_ARG(std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]) && std::isfinite(o[3]),
+                          "glowtts_adam_noam_groups: non-finite option (group %d)", k);
+        GLOWTTS_CHECK_ARG(o[0] >= 0.f, "glowtts_adam_noam_groups: lr_scale < 0 (group %d)", k);
+        GLOWTTS_CHECK_ARG(o[1] >= 0.f, "glowtts_adam_noam_groups: weight_decay < 0 (group %d)", k);
+        GLOWTTS_CHECK_ARG((o[2] == 0.f || o[2] == 1.f) && (o[3] == 0.f || o[3] == 1.f),
+                          "glowtts_adam_noam_groups: the decoupled and frozen flags must be 0 or 1 (group %d)", k);
+    }
+    GLOWTTS_CHECK_ARG(last == n, "glowtts_adam_noam_groups: the last group must end at n");
+    if (n == 0) return 0;
+    auto launch = guard != nullptr ? (e != nullptr ? launch_adam_groups<true, true> : launch_adam_groups<true, false>)
+                                   : (e != nullptr ? launch_adam_groups<false, true> : launch_adam_groups<false, false>);
+    launch(p, g, m, v, e, group_end, group_opts, n_groups, state, guard, lr, beta1, beta2, eps, dim_model, warmup, ema_rate, ema_warm,
+           ema_t0, (hipStream_t)stream);
+    GLOWTTS_LAUNCH_CHECK("glowtts_adam_noam_groups");
 }
 
 extern "C" int glowtts_adam_advance(float *state, float lr, float dim_model, float warmup, glowtts_stream_t stream) {

@@ -101,7 +101,7 @@ def save_checkpoint(checkpoint: Checkpoint, checkpoint_path: Path):
 def load_checkpoint(checkpoint_path: Path, config, model: typing.Optional[ModelType] = None,
                     optimizer: typing.Optional[OptimizerType] = None, load_optimizer: bool = True,
                     use_cuda: bool = True, ema_decay: typing.Optional[float] = None, ema_warmup: bool = False,
-                    use_ema: bool = False) -> Checkpoint:
+                    use_ema: bool = False, param_rules: typing.Optional[typing.Mapping[str, dict]] = None) -> Checkpoint:
     """Read a checkpoint written by this package or by the reference (reference checkpoint.py:51-106): model and
     optimizer are created from `config` unless passed in; model entries absent from the file keep their initial values
     (with a warning); missing counters default to version 1 / step 1 / learning rate 1.0.
@@ -111,14 +111,20 @@ def load_checkpoint(checkpoint_path: Path, config, model: typing.Optional[ModelT
     `"ema"` entries; a file without them (the reference's, or a run without the option) starts the average from the loaded
     weights, with a warning.
     `use_ema`: the MODEL is filled from `"model_ema"` instead of `"model"` — the averaged weights for synthesis; a file without
-    that entry raises KeyError."""
+    that entry raises KeyError.
+    `param_rules`: an optimizer created here gets the parameter groups `optimize.named_param_groups(model, param_rules)`, so a
+    fine-tuning run can start from a base checkpoint written with ONE group: the file's group supplies the moments of all
+    parameters by index and its rate, and the new groups keep the options the rules gave them.  A file with several groups
+    loads only into an optimizer with as many, of as many parameters each; any other count raises ValueError.  With equal
+    counts — ONE group into one group included — the file's options win over the rules': a file that carries no `lr_scale` /
+    `frozen` (no group used one) sets them to 1.0 / False.  Set other options in `optimizer._optim.param_groups` after loading."""
     saved = _read(checkpoint_path)
     if use_ema and "model_ema" not in saved:
         raise KeyError(f"{checkpoint_path}: no averaged weights (\"model_ema\") in this checkpoint; it was written without ema_decay")
     if ema_decay is not None and not load_optimizer:
         raise ValueError("load_checkpoint: ema_decay needs the optimizer (load_optimizer=True): it keeps the average")
     model, optimizer = setup_model(config, model=model, optimizer=optimizer, create_optimizer=load_optimizer,
-                                   use_cuda=use_cuda)
+                                   use_cuda=use_cuda, param_rules=param_rules)
     if load_optimizer and optimizer is not None:
         optimizer.load_state_dict(saved["optimizer"])
     target = _bare(model)

@@ -17,7 +17,7 @@ from torch.nn import functional as F
 from . import _hip, convops, monotonic_align, ops
 from .attentions import CouplingBlock, Encoder
 from .layers import ActNorm, ConvReluNorm, InvConvNear, LayerNorm
-from .optimize import OptimizerType
+from .optimize import OptimizerType, named_param_groups
 from .utils import generate_path, sequence_mask, squeeze, unsqueeze
 
 _actnorm_invconv_apply = _hip.direct_apply(ops.ActNormInvConvFn)
@@ -412,8 +412,11 @@ ModelType = FlowGenerator
 
 def setup_model(config, model: typing.Optional[ModelType] = None, optimizer: typing.Optional[OptimizerType] = None,
                 model_factory=ModelType, optimizer_factory=OptimizerType, create_optimizer: bool = True,
-                use_cuda: bool = True) -> typing.Tuple[ModelType, typing.Optional[OptimizerType]]:
-    """Build (or adopt) the model and its optimizer from a TrainingConfig-shaped object (reference models.py:417-470)."""
+                use_cuda: bool = True, *, param_rules: typing.Optional[typing.Mapping[str, dict]] = None
+                ) -> typing.Tuple[ModelType, typing.Optional[OptimizerType]]:
+    """Build (or adopt) the model and its optimizer from a TrainingConfig-shaped object (reference models.py:417-470).
+    `param_rules` (keyword-only, not the reference's): an optimizer built here gets the parameter groups
+    `optimize.named_param_groups(model, param_rules)` — frozen, rate-scaled or decayed parts of the model by name prefix."""
     if model is None:
         mc = config.model
         names = ("hidden_channels filter_channels filter_channels_dp kernel_size n_heads n_layers_enc p_dropout "
@@ -425,7 +428,8 @@ def setup_model(config, model: typing.Optional[ModelType] = None, optimizer: typ
     if use_cuda:
         model.cuda()
     if create_optimizer and optimizer is None:
-        optimizer = optimizer_factory(model.parameters(), scheduler=config.scheduler,
+        params = model.parameters() if param_rules is None else named_param_groups(model, param_rules)
+        optimizer = optimizer_factory(params, scheduler=config.scheduler,
                                       dim_model=config.model.hidden_channels, warmup_steps=config.warmup_steps,
                                       lr=config.learning_rate, betas=config.betas, eps=config.eps)
     return model, optimizer

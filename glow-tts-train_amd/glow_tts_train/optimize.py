@@ -6,11 +6,15 @@ restructured for MI355X: every parameter, gradient and moment lives in ONE flat 
   * gradient buckets for data-parallel all-reduce are plain slices of the flat gradient buffer (parallel.py),
   * the learning rate is derived on device from a step counter, so a captured hipGraph replays correctly,
   * an exponential moving average of the parameters (`ema_decay=`) is one more flat buffer streamed through the same update
-    kernel: no second pass over the parameters, no extra launch, no host work on the step path.
+    kernel: no second pass over the parameters, no extra launch, no host work on the step path,
+  * parameter groups (a rate scale, L2 or decoupled weight decay, "frozen") are contiguous ranges of the flat buffers, all updated
+    by that one launch; a frozen range is simply not streamed, and its parameters keep their gradient buffers.
 """
 from __future__ import annotations
 
 import contextlib
+import ctypes
+import math
 import typing
 import weakref
 from operator import is_ as _is
@@ -18,9 +22,10 @@ from operator import is_ as _is
 import numpy as np
 import torch
 
-from ._hip import call, ptr, weights_state
+from ._hip import CONSTANTS, call, ptr, weights_state
 
 _ALIGN = 64  # elements: every parameter starts on a 256-byte boundary of the flat buffers
+MAX_PARAM_GROUPS = CONSTANTS["GLOWTTS_MAX_PARAM_GROUPS"]
 
 
 def clip_launch(g: torch.Tensor, scale: float, clip_value: float, sumsq: torch.Tensor, guard: typing.Optional[torch.Tensor],
@@ -37,7 +42,7 @@ def clip_launch(g: torch.Tensor, scale: float, clip_value: float, sumsq: torch.T
 
 
 class FlatAdam(torch.optim.Optimizer):
-    """torch.optim.Adam arithmetic (no amsgrad / weight decay) over flat buffers, launched through the C ABI.
+    """torch.optim.Adam arithmetic (no amsgrad / maximize) over flat buffers, launched through the C ABI.
 
     `skip_nonfinite` (off by default): an update whose gradient holds a NaN or an Inf is skipped on the device, with no host
     read, so the step stays asynchronous and graph-capturable — the skip GradScaler.step gives the reference's fp16 runs
@@ -52,16 +57,40 @@ class FlatAdam(torch.optim.Optimizer):
     with a = 1 - decay, or with `ema_warmup` a = max(1 - decay, 9 / (10 + k)) for the k-th averaged update.  An update the
     device skips (`skip_nonfinite`) leaves the average and its count alone.  `ema_state_dict` / `swap_ema` hand the averaged
     weights out; `state_dict()` keeps torch's layout (checkpoint.py stores the average under keys of its own).  With the
-    option off nothing is allocated and nothing else is launched."""
+    option off nothing is allocated and nothing else is launched.
+
+    Parameter groups (`params` a list of torch-style group dicts, at most 8): each group is one contiguous range of the flat
+    buffers (the layout is group-major) and may set `weight_decay`, `decoupled_weight_decay` (torch.optim.Adam's own keys: L2
+    decay, or AdamW's), `lr_scale` (default 1.0: the group's rate is the shared rate times it, and the group's `lr` is a host
+    mirror of that) and `frozen` (default False: the update leaves the range alone and streams nothing of it; the parameters
+    keep their gradient buffers, so the native training path and the data-parallel buckets do not notice).  `betas` and `eps` are
+    shared.  The options are read at every `step()`, so they may be edited in `param_groups` between updates — but not under a
+    captured graph: the table is a by-value argument of the kernel, fixed when the launch is captured, so a replay applies the
+    options of the capture and an edit made afterwards is NOT honoured until the step is captured again.  While every
+    group is at its defaults, `step()` launches what an optimizer without groups launches; otherwise
+    glowtts_adam_noam_groups runs in place of the glowtts_adam_noam* call.  The clip pass does not know groups: the norm and,
+    with `skip_nonfinite`, the non-finite test cover the whole gradient buffer, so a NaN in a FROZEN group's gradient still
+    skips the update."""
 
     def __init__(self, params, lr=1.0, betas=(0.9, 0.98), eps=1e-9, dim_model: float = 0.0, warmup_steps: float = 0.0,
                  base_lr: typing.Optional[float] = None, skip_nonfinite: bool = False,
                  ema_decay: typing.Optional[float] = None, ema_warmup: bool = False):
         params = [p for p in params]
+        if params and isinstance(params[0], dict):
+            if len(params) > MAX_PARAM_GROUPS:
+                raise ValueError(f"FlatAdam: {len(params)} parameter groups, the update kernel takes at most {MAX_PARAM_GROUPS}")
+            if any("lr" in g for g in params):
+                raise ValueError("FlatAdam: a group's rate is the shared rate times its `lr_scale`; `lr` cannot be set per group")
         # the group carries every key torch.optim.Adam's does (amsgrad, weight_decay, foreach, ... at their defaults), so
         # state_dict() has torch's layout for this torch version and the reference loads it unchanged
         template = torch.optim.Adam([torch.zeros(1)], lr=lr, betas=betas, eps=eps).param_groups[0]
         super().__init__(params, {k: v for k, v in template.items() if k != "params"})
+        for g in self.param_groups:
+            if tuple(g["betas"]) != tuple(self.param_groups[0]["betas"]) or g["eps"] != self.param_groups[0]["eps"]:
+                raise ValueError("FlatAdam: betas and eps are shared by all parameter groups")
+        for k, (scale, _, _, _) in enumerate(self._group_options()):           # (raises on a negative or non-finite option)
+            if scale != 1.0:
+                self.param_groups[k]["lr"] = lr * scale                       # host mirror of the group's rate
         self.base_lr = float(lr if base_lr is None else base_lr)
         self.dim_model, self.warmup = float(dim_model), float(warmup_steps)
         self.guard: typing.Optional[torch.Tensor] = None
@@ -91,6 +120,13 @@ class FlatAdam(torch.optim.Optimizer):
             total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
         self.offsets, self.numel_padded = offs, total
         self.numel = sum(p.numel() for p in ps)
+        # the layout is group-major, so every group is ONE range of the flat buffers: group k ends where its last parameter's
+        # padding does (multiples of _ALIGN: the update kernel keeps its 16-byte form)
+        counts = np.cumsum([len(g["params"]) for g in self.param_groups])
+        self.group_ends = [total if c == len(ps) else offs[c] for c in counts]
+        # host arrays of glowtts_adam_noam_groups, read during the call only
+        self._group_end = (ctypes.c_int64 * len(self.group_ends))(*self.group_ends)
+        self._group_opts = (ctypes.c_float * (4 * len(self.group_ends)))()
         self.flat_p = torch.zeros(total, device=dev, dtype=dt)
         self.flat_g = torch.zeros(total, device=dev, dtype=dt)
         self.flat_m = torch.zeros(total, device=dev, dtype=dt)
@@ -122,6 +158,25 @@ class FlatAdam(torch.optim.Optimizer):
     def slices(self):
         """(offset, numel) of every parameter inside the flat buffers, in construction order."""
         return [(o, p.numel()) for p, o in zip(self._params, self.offsets)]
+
+    # -- parameter groups ---------------------------------------------------------------------------------------
+    def _group_options(self) -> typing.List[typing.Tuple[float, float, bool, bool]]:
+        """(lr_scale, weight_decay, decoupled, frozen) of every group, as the groups say NOW (they may be edited between updates);
+        a negative or non-finite lr_scale / weight_decay raises ValueError."""
+        out = []
+        for k, g in enumerate(self.param_groups):
+            scale, decay = float(g.get("lr_scale", 1.0)), float(g["weight_decay"])
+            if not (math.isfinite(scale) and math.isfinite(decay) and scale >= 0.0 and decay >= 0.0):
+                raise ValueError(f"FlatAdam: group {k}: lr_scale = {scale} and weight_decay = {decay} must be finite and >= 0")
+            out.append((scale, decay, bool(g.get("decoupled_weight_decay", False)), bool(g.get("frozen", False))))
+        return out
+
+    def _all_default(self) -> bool:
+        """Every group at lr_scale 1, no decay, not frozen: the update is the one an optimizer without groups launches."""
+        for g in self.param_groups:
+            if g["weight_decay"] != 0 or g.get("lr_scale", 1.0) != 1.0 or g.get("frozen", False):
+                return False
+        return True
 
     # -- exponential moving average of the parameters -----------------------------------------------------------
     def enable_ema(self, decay: float, warmup: bool = False, num_updates: int = 0) -> None:
@@ -277,7 +332,13 @@ class FlatAdam(torch.optim.Optimizer):
         rates = (self.base_lr, float(b1), float(b2), float(g["eps"]), self.dim_model, self.warmup)
         guarded = "_guarded" if self.guard is not None else ""
         guard = (ptr(self.guard),) if guarded else ()
-        if self.flat_e is not None:                   # the same update with the average carried along; its guard may be NULL
+        if not self._all_default():                   # some group has options of its own: the grouped form of the same update
+            for k, (scale, decay, decoupled, frozen) in enumerate(self._group_options()):
+                self._group_opts[4 * k: 4 * k + 4] = (scale, decay, float(decoupled), float(frozen))
+            call("glowtts_adam_noam_groups", *buffers, ptr(self.flat_e), self.numel_padded, ptr(self.dev_state), ptr(self.guard),
+                 *rates, self._ema_rate, int(self.ema_warmup), self._ema_t0, ctypes.addressof(self._group_end),
+                 ctypes.addressof(self._group_opts), len(self.group_ends))
+        elif self.flat_e is not None:                 # the same update with the average carried along; its guard may be NULL
             call("glowtts_adam_noam_ema", *buffers, ptr(self.flat_e), self.numel_padded, ptr(self.dev_state), ptr(self.guard), *rates,
                  self._ema_rate, int(self.ema_warmup), self._ema_t0)
         else:
@@ -298,7 +359,16 @@ class FlatAdam(torch.optim.Optimizer):
                 "exp_avg_sq": self.flat_v[o:o + n].view(p.shape).clone(),
             }
         groups = [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups]
-        groups[0]["params"] = list(range(len(self._params)))
+        # `lr_scale` / `frozen` are this package's keys: a file carries them only when some group uses one (then every group
+        # does), so an optimizer without them writes exactly torch.optim.Adam's keys
+        special = any(g.get("lr_scale", 1.0) != 1.0 or g.get("frozen", False) for g in groups)
+        first = 0
+        for g, own in zip(groups, self.param_groups):
+            scale, frozen = g.pop("lr_scale", 1.0), g.pop("frozen", False)
+            if special:
+                g["lr_scale"], g["frozen"] = float(scale), bool(frozen)
+            g["params"] = list(range(first, first + len(own["params"])))       # group-major, as torch numbers them
+            first += len(own["params"])
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, d):
@@ -306,15 +376,26 @@ class FlatAdam(torch.optim.Optimizer):
         optimizer's raises ValueError; an EMPTY state (a file saved before the first update) is accepted, and so is a
         state without an entry for some parameter — torch.optim.Adam only creates a parameter's state at its first
         gradient, so a reference checkpoint of a model with a frozen / never-used parameter has none: zero moments here,
-        with a warning."""
+        with a warning.  A state of ONE group loads into an optimizer of several (its moments by parameter index; this
+        optimizer's group options stay); several groups in the file must be as many as here and hold as many parameters
+        each, else ValueError.  With as many groups as here the FILE's options win, a missing `lr_scale` / `frozen` included:
+        state_dict() writes the two only when some group uses one, so their absence says 1.0 / False."""
         st = d.get("state", {})
         saved_groups = d.get("param_groups", [])
         # the average counts its updates from the device's Adam step, which this call may move: the count itself stays
         ema_seen = self.ema_num_updates() if self.flat_e is not None else None
+        if len(saved_groups) > 1 and len(saved_groups) != len(self.param_groups):
+            raise ValueError(f"loaded state dict has {len(saved_groups)} parameter groups, the optimizer has {len(self.param_groups)}: "
+                             "only a single-group state can be spread over other groups")
         if saved_groups and "params" in saved_groups[0]:
             n_saved = sum(len(g["params"]) for g in saved_groups)
             if n_saved != len(self._params):
                 raise ValueError(f"loaded state dict has {n_saved} parameters, the optimizer has {len(self._params)}")
+            # several groups: the file's options belong to the parameters they were saved for (torch.optim raises here too)
+            sizes, own_sizes = [len(g["params"]) for g in saved_groups], [len(g["params"]) for g in self.param_groups]
+            if len(saved_groups) > 1 and sizes != own_sizes:
+                raise ValueError(f"loaded state dict has parameter groups of {sizes} parameters, the optimizer's have {own_sizes}")
+        same_groups = len(saved_groups) == len(self.param_groups)
         missing = [i for i in range(len(self._params)) if st and i not in st and str(i) not in st]
         if missing:
             import warnings
@@ -347,19 +428,45 @@ class FlatAdam(torch.optim.Optimizer):
                 self.dev_state[0] = max(steps) + 1.0
                 if ema_seen is not None:
                     self._ema_t0 = max(steps) + 1.0 - ema_seen
-        for g_new, g in zip(d.get("param_groups", []), self.param_groups):
-            for k in ("lr", "betas", "eps"):
-                if k in g_new:
-                    g[k] = g_new[k]
+        # The groups.  As many in the file as here: every group takes its options from the file.  ONE group in the file and several
+        # here (fine-tuning from a base checkpoint): the file's moments were matched by index above, its betas / eps are shared, and
+        # the options this optimizer was built with stay.
+        if same_groups:
+            for g_new, g in zip(saved_groups, self.param_groups):
+                for k in ("lr", "betas", "eps", "weight_decay", "decoupled_weight_decay"):
+                    if k in g_new:
+                        g[k] = g_new[k]
+                # state_dict() leaves these two out when every group has them at their defaults (and a file of the reference or
+                # from before the groups never has them): absent means 1.0 / False, not "keep this optimizer's"
+                for k in ("lr_scale", "frozen"):
+                    if k in g_new:
+                        g[k] = g_new[k]
+                    else:
+                        g.pop(k, None)
+        elif len(saved_groups) == 1:
+            for g in self.param_groups:
+                for k in ("betas", "eps"):
+                    if k in saved_groups[0]:
+                        g[k] = saved_groups[0][k]
+        options = self._group_options()
         # torch.optim.Adam.load_state_dict leaves the stored group lr in force until the schedule next writes it, i.e.
-        # for exactly one update under "noam" (reference optimize.py:43-48, :60-61) and for good otherwise
-        groups = d.get("param_groups", [])
-        if groups and "lr" in groups[0]:
-            lr = float(groups[0]["lr"])
-            if self.warmup > 0.0:
-                self.dev_state[3] = lr
-            else:
-                self.base_lr = lr
+        # for exactly one update under "noam" (reference optimize.py:43-48, :60-61) and for good otherwise.  What is imposed is
+        # a BASE rate (the kernel scales it per group): the stored rate of the first live group with a rate, over the lr_scale
+        # it was SAVED at (the file's, which with as many groups as here is now this optimizer's too; 1.0 for a one-group file
+        # spread over several).  Every group's `lr` mirror is then that base rate times the group's own scale: what the kernel
+        # applies, whatever the file's other `lr` entries say.
+        saved_options = options if same_groups else [(1.0, 0.0, False, False)] * len(saved_groups)
+        for g_new, (saved_scale, _, _, frozen) in zip(saved_groups, saved_options):
+            if "lr" in g_new and saved_scale > 0.0 and not frozen:
+                saved_lr = float(g_new["lr"])
+                lr = saved_lr / saved_scale
+                if self.warmup > 0.0:
+                    self.dev_state[3] = lr
+                else:
+                    self.base_lr = lr
+                for g, (scale, _, _, _) in zip(self.param_groups, options):
+                    g["lr"] = saved_lr if scale == saved_scale else lr * scale     # (x / s * s need not be x)
+                break
 
 
 def _check_decay(decay) -> float:
@@ -373,7 +480,8 @@ class Adam:
     """Reference surface (optimize.py:8-64): `Adam(params, scheduler, dim_model, warmup_steps, lr, betas, eps)` with
     `.step() .zero_grad() .get_lr() .state_dict() .load_state_dict() .cur_lr .step_num ._optim`.  Keyword-only additions:
     `skip_nonfinite`, `ema_decay`, `ema_warmup` (FlatAdam); `enable_ema`, `ema_num_updates`, `ema_state_dict` and `swap_ema`
-    are FlatAdam's."""
+    are FlatAdam's.  `params` may be a list of parameter-group dicts (FlatAdam; `named_param_groups` builds one from name
+    prefixes): every group's `lr` then mirrors `cur_lr` times its `lr_scale`."""
 
     def __init__(self, params, scheduler, dim_model, warmup_steps: int = 4000, lr: float = 1e0,
                  betas: typing.Tuple[float, float] = (0.9, 0.98), eps: float = 1e-9, *, skip_nonfinite: bool = False,
@@ -400,7 +508,7 @@ class Adam:
         if self.scheduler == "noam":
             self.cur_lr = self.lr * self._get_lr_scale()
             for group in self._optim.param_groups:
-                group["lr"] = self.cur_lr
+                group["lr"] = self.cur_lr * group.get("lr_scale", 1.0)
 
     def get_lr(self):
         return self.cur_lr
@@ -443,7 +551,7 @@ class Adam:
                 self.cur_lr = self.lr * self._get_lr_scale()
                 for group in flat.param_groups:
                     # a rate a resumed checkpoint imposed on the next update (dev_state[3]) is still pending after a skip
-                    group["lr"] = host[3] if host[3] > 0.0 else self.cur_lr
+                    group["lr"] = (host[3] if host[3] > 0.0 else self.cur_lr) * group.get("lr_scale", 1.0)
         return {"applied": int(host[7]), "skipped": int(host[5]), "consecutive_skipped": int(host[6])}
 
     def load_state_dict(self, d):
@@ -452,6 +560,33 @@ class Adam:
 
     def state_dict(self):
         return self._optim.state_dict()
+
+
+def named_param_groups(model: torch.nn.Module, rules: typing.Optional[typing.Mapping[str, dict]],
+                       default: typing.Optional[dict] = None) -> typing.List[dict]:
+    """Parameter groups for `Adam` / `FlatAdam` from name prefixes: `rules` maps a prefix of `model.named_parameters()` names to
+    group options, e.g. {"encoder.": {"frozen": True}, "decoder.": {"lr_scale": 0.5, "weight_decay": 1e-2,
+    "decoupled_weight_decay": True}}.  The LONGEST matching prefix wins; parameters no prefix matches form one group with the
+    `default` options; a prefix that matches no parameter raises ValueError, and so does one that loses every parameter it
+    matches to longer prefixes (its group would be empty).  One group per rule, emitted in the order in
+    which the groups first appear in `named_parameters()`.
+
+    The flat layout is group-major, so rules by MODULE prefix keep it in model order, which `parallel.FlowBlockReducer`
+    requires.  Rules that interleave the groups through the model (every bias, say) are fine on one GPU, but the reducer then
+    raises its "order differs from the optimizer's flat layout" error."""
+    rules = dict(rules or {})
+    members: typing.Dict[typing.Optional[str], list] = {}
+    for name, p in model.named_parameters():
+        hits = [prefix for prefix in rules if name.startswith(prefix)]
+        members.setdefault(max(hits, key=len) if hits else None, []).append(p)
+    names = [name for name, _ in model.named_parameters()]
+    unused = [prefix for prefix in rules if not any(name.startswith(prefix) for name in names)]
+    if unused:
+        raise ValueError(f"named_param_groups: no parameter name starts with {unused}")
+    shadowed = [prefix for prefix in rules if prefix not in members]
+    if shadowed:
+        raise ValueError(f"named_param_groups: every parameter under {shadowed} is taken by a longer prefix of the rules")
+    return [{"params": ps, **(dict(default or {}) if prefix is None else rules[prefix])} for prefix, ps in members.items()]
 
 
 OptimizerType = Adam

@@ -39,20 +39,23 @@ _LOGGER = logging.getLogger("glow_tts_train")
 
 def train(train_loader, config, model_dir: Path, model=None, optimizer=None, global_step: int = 1,
           checkpoint_epochs: int = 1, rank: int = 0, reducer=None, accum_steps: int = 1, skip_nonfinite: bool = False,
-          ema_decay: typing.Optional[float] = None, ema_warmup: bool = False):
+          ema_decay: typing.Optional[float] = None, ema_warmup: bool = False,
+          param_rules: typing.Optional[typing.Mapping[str, dict]] = None):
     """Epoch loop of the reference (train.py:19-88): seed, build or adopt model and optimizer, run `config.epochs`
     passes over `train_loader`, and on rank 0 write `checkpoint_<step>.pth` + `config_<step>.json` into `model_dir`
     every `checkpoint_epochs` epochs.  Returns the final global step.  `accum_steps`: loader batches per update (train_step).
     `skip_nonfinite`: skip updates whose gradient is not finite (train_step); an optimizer built here gets the option switched
     on, one passed in must have been built with it.  `ema_decay` / `ema_warmup`: keep an exponential moving average of the
     weights (optimize.FlatAdam); an optimizer built here gets it switched on, one passed in is taken as it is.  The checkpoints
-    of an averaging optimizer carry the average."""
+    of an averaging optimizer carry the average.  `param_rules`: an optimizer built here is built from
+    `optimize.named_param_groups(model, param_rules)` (frozen / rate-scaled / decayed parts of the model by name prefix: fine-tuning
+    from a base checkpoint); one passed in is taken as it is."""
     from .checkpoint import Checkpoint, save_checkpoint
     from .models import setup_model
 
     torch.manual_seed(config.seed)
     built_here = optimizer is None
-    model, optimizer = setup_model(config, model=model, optimizer=optimizer)
+    model, optimizer = setup_model(config, model=model, optimizer=optimizer, param_rules=param_rules)
     assert model is not None and optimizer is not None
     if skip_nonfinite and built_here:
         optimizer._optim.enable_skip_nonfinite()

@@ -943,7 +943,28 @@ int glowtts_span_logw(const int32_t *first, const int32_t *t_x, float *logw_, in
  *        != 0: a = max(ema_rate, 9 / (10 + k)), k = state[0] - ema_t0 the number of averaged updates so far (0 for the first), read
  *        from device memory — a captured graph replays with the right weight, a skipped update does not count, and
  *        adam_advance / adam_advance_guarded follow unchanged.  Elements with p = e = 0 and g = m = v = 0 stay exactly zero.
- * swap_f32 : exchanges two equally long buffers in one pass; overlapping buffers are refused. */
+ * swap_f32 : exchanges two equally long buffers in one pass; overlapping buffers are refused.
+ *
+ * adam_groups : the update over parameter GROUPS — contiguous ranges of the flat buffers with options of their own.  e may be NULL
+ *        (no average) and guard may be NULL; both mean what they mean in adam_ema.  group_end and group_opts are HOST arrays, read
+ *        during the call: what the kernel needs of them is copied into its arguments by value, nothing is read after the call
+ *        returns, and a captured graph replays with the table it was captured with.  group_end[k] is the exclusive end of group k
+ *        in elements, ascending, group_end[n_groups - 1] == n; an empty group is allowed.  group_opts[4k .. 4k+3] = {lr_scale,
+ *        weight_decay, decoupled (0 / 1), frozen (0 / 1)}; 1 <= n_groups <= GLOWTTS_MAX_PARAM_GROUPS.  Null pointers, n_groups out
+ *        of range, ends that do not ascend or do not end at n, lr_scale < 0, weight_decay < 0, a non-finite option and a flag that
+ *        is neither 0 nor 1 are refused before anything is launched.
+ *        t, the rate lr_t of adam, both bias corrections, beta1, beta2 and eps are shared by every group.  Per element of group k:
+ *          frozen — p, m, v, e of the range are neither read nor written, and nobody reads its g: the ONE launch covers the live
+ *                   ranges only;
+ *          else   — rate_k = fl32(lr_t * lr_scale), step_size_k = rate_k / (1 - beta1^t) as adam forms its own from lr_t;
+ *                   decoupled decay (torch.optim.Adam(decoupled_weight_decay=True), AdamW): p *= 1 - rate_k weight_decay first;
+ *                   L2 decay: g' = g + weight_decay p goes into the moments; weight_decay == 0 takes the plain expressions (a
+ *                   select, not arithmetic with a zero); then the update and, with e, the average as in adam_ema.
+ *        A group with lr_scale = 1 and weight_decay = 0 comes out bit for bit as from adam / adam_guarded / adam_ema on that range;
+ *        lr_scale = 0 moves the moments and leaves p bit for bit; elements with p = g = m = v = 0 stay exactly zero under both
+ *        decays.  16-byte access is used only when every group end is a multiple of 4 as well.  The clip pass and adam_advance /
+ *        adam_advance_guarded are unchanged: the norm and the non-finite test still cover frozen ranges. */
+#define GLOWTTS_MAX_PARAM_GROUPS 8
 int glowtts_clip_grad_value(float *g, int64_t n, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_clip_grad_value_scaled(float *g, int64_t n, float scale, float clip, float *sumsq, glowtts_stream_t stream);
 int glowtts_adam_noam(float *p, const float *g, float *m, float *v, int64_t n, const float *state, float lr,
@@ -961,6 +982,10 @@ int glowtts_adam_noam_ema(float *p, const float *g, float *m, float *v, float *e
                           const float *guard, float lr, float beta1, float beta2, float eps, float dim_model, float warmup,
                           float ema_rate, int ema_warm, float ema_t0, glowtts_stream_t stream);
 int glowtts_swap_f32(float *a, float *b, int64_t n, glowtts_stream_t stream);
+int glowtts_adam_noam_groups(float *p, const float *g, float *m, float *v, float *e, int64_t n, const float *state,
+                             const float *guard, float lr, float beta1, float beta2, float eps, float dim_model, float warmup,
+                             float ema_rate, int ema_warm, float ema_t0, const int64_t *group_end, const float *group_opts,
+                             int n_groups, glowtts_stream_t stream);
 
 #ifdef __cplusplus
 }
